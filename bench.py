@@ -1,6 +1,16 @@
 """Benchmark of the mi355x mode's hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C1|C3|C4|C5|target64]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+input, warms up, times the K steps, writes the last step's results if
+--dump-outputs is given (DIR/<op>.npy, see dump_outputs) and prints the line
+with `value`, `ms_per_step` and the permute kernel's `roofline` (its hipEvents
+are part of the timed step).  Everything below that takes runs of its own --
+per-op and statistics rooflines, the copy ceiling, the checks, PMC traffic,
+the sub-records, the CPU baseline, the profiler and the sweeps at N > 1, the
+detail file -- is measured with --full.
 
 One "step" = one pass of the hot path over one batch of synthetic input,
 resident in HBM before timing starts.  Default workload (BASELINE.json
@@ -15,7 +25,7 @@ dominant kernel (the swap's permute) measured with hipEvents on the stream it
 runs on; `stats_roofline` the same for the reduction kernels of mean / std;
 traffic comes from rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE).
 
-Sub-records of the default run (same JSON line; `value` stays C2's):
+Sub-records of the default --full run (same JSON line; `value` stays C2's):
   configs   C1, C3, C4 and C5 (BASELINE configs[0], [2..4]) on their GLOBAL
             shapes (strong scaling: N slabs of the leading axis), a few steps
             each: value, per-op time, fraction of HBM peak, PMC traffic;
@@ -87,6 +97,14 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-op and statistics rooflines, "
+                         "the copy ceiling, the checks of every op, PMC traffic, the target64 and "
+                         "C1/C3/C4/C5 sub-records, the CPU baseline, at N > 1 the profiler and the sweeps; "
+                         "writes the detail file (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what every op of the last timed step returned "
+                         "to DIR/<op>.npy (float32 / float64; a fixed seeded sample of a large result)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-rows", type=int, default=None)
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc traffic passes")
@@ -233,6 +251,12 @@ def synth_shard(torch, shape, dtype, device, seed):
     raise ValueError(dtype)
 
 
+def _put(d, k, v):
+    """d[k] = v, returning v: an op whose result the next op reads still hands it to its caller."""
+    d[k] = v
+    return v
+
+
 def steps_of(cfg, b, world=1):
     """The step of a config as (name, call, algorithmic bytes per rank) in order.
 
@@ -246,12 +270,12 @@ def steps_of(cfg, b, world=1):
     if cfg == "C2":
         out = b.shape[1] * b.shape[2] * 4 // world
         sw = {}
-        return [("swap", lambda: sw.__setitem__("s", b.swap((0,), (0, 1))), 2 * N),
+        return [("swap", lambda: _put(sw, "s", b.swap((0,), (0, 1))), 2 * N),
                 ("mean", lambda: sw["s"].mean(axis=2), N + out),
                 ("std", lambda: sw["s"].std(axis=2), N + out)]
     if cfg == "C1":
         sw = {}
-        ops = [("swap", lambda: sw.__setitem__("s", b.swap((0,), (0,))), 2 * N)]
+        ops = [("swap", lambda: _put(sw, "s", b.swap((0,), (0,))), 2 * N)]
         for name in ("sum", "mean", "var", "std"):
             for ax in (None, (0,)):
                 nout = 1 if ax is None else n * world // b.shape[1]
@@ -278,7 +302,7 @@ def steps_of(cfg, b, world=1):
         moved = 0 if geom.is_identity() else N + P
         ck = {}
         return [("swap", lambda: b.swap((0,), (0,)), 2 * N),
-                ("chunk", lambda: ck.__setitem__("c", b.chunk("150")), moved),
+                ("chunk", lambda: _put(ck, "c", b.chunk("150")), moved),
                 ("unchunk", lambda: ck.pop("c").unchunk(), moved),
                 ("var", lambda: b.var(axis=0), N + (n * world // b.shape[0]) * 8)]
     if cfg == "C5":
@@ -290,7 +314,7 @@ def steps_of(cfg, b, world=1):
         ck = {}
         return [("T", lambda: b.T, 2 * N),
                 ("transpose", lambda: b.transpose(2, 0, 4, 1, 3), 2 * N),
-                ("chunk", lambda: ck.__setitem__("c", b.chunk((16, 16), padding=2)), N + P),
+                ("chunk", lambda: _put(ck, "c", b.chunk((16, 16), padding=2)), N + P),
                 ("unchunk", lambda: ck["c"].unchunk(), P + N),
                 ("keys_to_values", lambda: ck["c"].keys_to_values((2,)), 2 * P),
                 ("values_to_keys", lambda: ck.pop("c").values_to_keys((0,)), P + Pv)]
@@ -660,9 +684,9 @@ def rocprof_path():
 
 
 def rocprof_wanted(args, world, where):
-    """True on EVERY rank of an N-rank GPU run whose rank 0 runs under
+    """True on EVERY rank of an N-rank --full GPU run whose rank 0 runs under
     rocprofv3 (all ranks then run the marked pass, which holds collectives)."""
-    return (world > 1 and not args.no_rocprof and not args.pmc_child and where != "cpu"
+    return (args.full and world > 1 and not args.no_rocprof and not args.pmc_child and where != "cpu"
             and os.environ.get("BOLT_AMD_BENCH_ROCPROF", "1") != "0" and rocprof_path() is not None)
 
 
@@ -1276,6 +1300,53 @@ def compact_cpu(cb):
     return out
 
 
+DUMP_BYTES = 60 << 20   # all files of one --dump-outputs together (the limit is 64 MB)
+DUMP_SEED = 20240
+
+
+def host_output(r):
+    """What an op call returned, as a flat-or-shaped host ndarray: a statistic
+    is one already; an array of the mode is read back whole (toarray: across
+    GPUs every rank takes part, the result is the global array); a chunked
+    array gives this rank's packed records.  None if the op returned nothing."""
+    from bolt_amd.mi355x.transfer import to_host
+    if r is None:
+        return None
+    if hasattr(r, "_packed"):
+        return to_host(r._packed, r.dtype, (r._packed.numel() // r.dtype.itemsize,))
+    if hasattr(r, "toarray"):
+        return np.asarray(r.toarray())
+    return np.asarray(r)
+
+
+def dump_outputs(outdir, kept, write=True):
+    """--dump-outputs: ``kept`` is [(op, result)] of the last timed step, in the
+    step's order.  Each result goes to outdir/<op>.npy as float32 (float32 and
+    narrower results, exactly) or float64.  The files share DUMP_BYTES: a result
+    over its share is reduced to the elements at DUMP_SEED's sorted random flat
+    indices -- the same indices in every run of the same arguments -- and comes
+    out 1-D.  Returns {op: [elements written, elements of the result]}."""
+    share = DUMP_BYTES // max(1, len(kept))
+    if write:
+        os.makedirs(outdir, exist_ok=True)
+    done = {}
+    for k, (name, r) in enumerate(kept):
+        a = host_output(r)
+        if a is None:
+            continue
+        wide = np.float32 if a.dtype.kind in "fiub" and a.dtype.itemsize <= (4 if a.dtype.kind == "f" else 2) \
+            else np.float64
+        n, total = share // np.dtype(wide).itemsize, int(a.size)
+        if total > n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + k).integers(0, total, size=n))
+            a = a.reshape(-1)[idx]
+        done[name] = [int(a.size), total]
+        if write:
+            np.save(os.path.join(outdir, "%s.npy" % name), np.ascontiguousarray(a, dtype=wide))
+        del a
+    return done
+
+
 def detail_path(args, world):
     p = args.detail or os.path.join("gpurun_out", "bench_detail_n%d.json" % world)
     return p if os.path.isabs(p) else os.path.join(HERE, p)
@@ -1375,9 +1446,10 @@ def main():
         gc.collect()
         _empty_cache(torch, dev)
 
-    def timed_steps(ops, steps, clock=None, call_events=None, op_filter=None):
+    def timed_steps(ops, steps, clock=None, call_events=None, op_filter=None, keep=None):
         """K steps between barriers; the clock / call events (when given) time the
-        ops op_filter admits.  Returns the max-over-ranks wall time."""
+        ops op_filter admits; ``keep`` (a list) receives (op, result) of the last
+        step's calls.  Returns the max-over-ranks wall time."""
         barrier()
         t0 = time.perf_counter()
         for i in range(steps):
@@ -1394,6 +1466,8 @@ def main():
                     call_events.setdefault(name, []).append((e0, e1))
                 if clock is not None:
                     clock.op = None
+                if keep is not None and i == steps - 1:
+                    keep.append((name, r))
                 del r
         barrier()
         return max_over_ranks(time.perf_counter() - t0)
@@ -1502,9 +1576,10 @@ def main():
             rec_ops.setdefault(name, {})["ck"] = v
         return ok
 
-    def measure_main(cfg, steps, warmup):
+    def measure_main(cfg, steps, warmup, dump_to=None):
         """The headline record: wall time of K steps, the permute kernel's own
-        hipEvents (one GPU) or the exchange's (N GPUs), per-op times, checks."""
+        hipEvents (one GPU) or the exchange's (N GPUs); with --full per-op
+        times and checks.  ``dump_to``: directory of --dump-outputs."""
         b, gshape, dtype, split, scaling, desc = build(cfg)
         ops = steps_of(cfg, b, world)
         if args.pmc_child:  # profiled child of pmc_traffic(): the step, a marker before every op
@@ -1528,8 +1603,9 @@ def main():
         swap_ev = {} if world > 1 else None
         if world > 1:
             bdist.PROFILE = {}  # hipEvent pairs around pack / all_to_all / unpack
+        kept = [] if dump_to else None
         try:
-            elapsed = timed_steps(ops, steps, clock=clock, call_events=swap_ev, op_filter=(ops[0][0],))
+            elapsed = timed_steps(ops, steps, clock=clock, call_events=swap_ev, op_filter=(ops[0][0],), keep=kept)
         finally:
             clock.close()
         phases, rccl_ms = {}, None
@@ -1540,6 +1616,11 @@ def main():
                 # the RCCL groups alone (all pipeline stages of a swap), per swap
                 rccl_ms = float(np.sum([a.elapsed_time(z) for a, z in bdist.PROFILE["rccl"]])) / steps
             bdist.PROFILE = None
+        dumped = None
+        if dump_to:
+            progress("%s: writing the last timed step's results to %s" % (cfg, dump_to))
+            dumped = dump_outputs(dump_to, kept, write=rank == 0)
+            del kept[:]
         # On one GPU the swap call is the one permute launch, so only the kernel's
         # own event pair is recorded (each extra stream event adds a few us between
         # the kernels); across GPUs the call's pair brackets the whole exchange.
@@ -1620,6 +1701,13 @@ def main():
             else:
                 line["rccl_ranks"] = None
         line["roofline"]["frac_of_measured_copy"] = round(line["roofline"]["achieved"] / HBM_COPY_GBPS, 4)
+        if dumped is not None:
+            line["outputs"] = {"dir": dump_to, "elements": dumped}
+        if not args.full:
+            # a plain run ends here: everything below takes runs of its own
+            del b, ops
+            release()
+            return line
         # this box's own copy ceiling for the same bytes (boxes differ by up to
         # ~25% on the same kernel, profiles/r06zk_pack_expand.log)
         copy_live = live_copy_gbps(be, dev, ops[0][2] // 2) if world == 1 else None
@@ -1710,10 +1798,11 @@ def main():
                     rec["tr"] = round(traffic[k] / nb, 4)
         return traffic
 
-    line = measure_main(args.config, args.steps, args.warmup)
+    line = measure_main(args.config, args.steps, args.warmup, dump_to=args.dump_outputs)
     if line is None:
         return 0
-    one = rank == 0 and world == 1 and dev.type == "cuda"
+    # (everything from here to the record's assembly belongs to --full)
+    one = args.full and rank == 0 and world == 1 and dev.type == "cuda"
     if one and not args.no_pmc:
         names = list(line["config"]["bytes_per_step"])
         recs = {n: [line["ops"][n]] for n in names if n in line["ops"]}
@@ -1725,7 +1814,7 @@ def main():
             line["roofline"]["traffic"] = int(traffic[0])
             line["roofline"]["traffic_ratio"] = line["roofline"].pop("tr", None)
     target = None
-    if world == 1 and args.config == "C2" and not args.no_target64:
+    if args.full and world == 1 and args.config == "C2" and not args.no_target64:
         # BASELINE.json's target sentence: swap and statistics of a 64 GiB
         # float32 4-D array on one GPU at >= 60% of the HBM roofline
         t = measure_main("target64", args.target_steps, 1)
@@ -1742,7 +1831,7 @@ def main():
             add_traffic("target64", names, recs)
             target["roofline"]["traffic_ratio"] = target["roofline"].pop("tr", None)
     configs = None
-    if args.config == "C2" and not args.no_configs:
+    if args.full and args.config == "C2" and not args.no_configs:
         configs = {}
         for cfg in SUB_CONFIGS:
             rec = measure_sub(cfg, args.config_steps, 1)
@@ -1761,18 +1850,22 @@ def main():
     checks_ok = out.pop("checks_ok", None)
     if cpu is not None:
         out["cpu_baseline"] = compact_cpu(cpu)
-    out["ops"] = ops
+    if args.full:
+        out["ops"] = ops
     if configs is not None:
         out["configs"] = configs
     if target is not None:
         out["target64"] = target
     if stats_roofline is not None:
         out["stats_roofline"] = stats_roofline
-    out["checks_ok"] = checks_ok
+    if args.full:
+        out["checks_ok"] = checks_ok
     if profiling:
         out["rocprof_marks"] = marks
         out["rocprof_info"] = marks_info
-    if rank == 0:
+    if rank == 0 and not (args.full or args.detail):
+        print(json.dumps(out, separators=(",", ":")), flush=True)
+    elif rank == 0:
         path = detail_path(args, world)
         try:
             os.makedirs(os.path.dirname(path), exist_ok=True)

@@ -192,14 +192,54 @@ def _every_op_checked(rec):
     assert all(o["ck"] == "exact" or o["ck"].startswith("ok ") for o in rec["ops"].values()), rec["ops"]
 
 
+FULL_ONLY = ("ops", "stats_roofline", "checks_ok", "configs", "target64", "cpu_baseline", "detail", "rocprof",
+             "a2a", "exchange_check", "rocprof_marks")
+
+
+def _plain(args, env_extra):
+    """A run without --full on the CPU rehearsal -> (its one JSON line, its progress lines)."""
+    r = _bench(args + ["--shapes", SHAPES], dict(env_extra, BOLT_AMD_BENCH_DEVICE="cpu"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in FULL_ONLY:  # none of --full's records, passes or files
+        assert k not in d, k
+    assert "copy_live" not in d["roofline"]
+    return d, [ln for ln in r.stderr.splitlines() if ln.startswith("[bench ")]
+
+
+def _input(cfg, world=1):
+    """The bench's global input of a config at SHAPES, rebuilt the bench's way
+    (rank r's slab from seed 1234 + r; a weak config's shape is one rank's)."""
+    sys.path[:0] = [HERE, ROOT]
+    import torch
+    import bench
+    a = bench.parse(["--shapes", SHAPES])
+    gshape, dtype = bench.config_of(a, cfg, world)[:2]
+    slabs = bench.slab_shapes(gshape, world)
+    return np.concatenate([bench.synth_shard(torch, slabs[r], dtype, torch.device("cpu"), 1234 + r).numpy()
+                           for r in range(world)], axis=0)
+
+
 @pytest.mark.parametrize("world", [2, 3, 4])
-def test_bench_launches_its_ranks(world):
-    """`bench.py --gpus N` without WORLD_SIZE starts the N rank processes itself
+def test_bench_launches_its_ranks(world, tmp_path):
+    """`bench.py --full --gpus N` without WORLD_SIZE starts the N rank processes itself
     and rank 0's JSON line comes back: n_gpus N, the C2 headline weak-scaled,
     C1/C3/C4/C5 strong-scaled on their global shapes (3 ranks: ragged and empty
     slabs), every op of every step checked (the CPU rehearsal: test executor
-    over gloo, tiny shapes)."""
-    r = _bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-pmc", "--no-cpu-baseline",
+    over gloo, tiny shapes).  Without --full the same launch measures the
+    headline and the exchange's phases only, and --dump-outputs writes the
+    global results, gathered from every rank."""
+    d, _ = _plain(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                  {"BOLT_AMD_BENCH_BACKEND": "gloo"})
+    assert d["n_gpus"] == world and d["steps"] == 2 and d["config"]["global_shape"] == [4 * world, 8, 8]
+    assert d["ms_per_step"] > 0 and "phases_ms" in d["xgmi"] and "stages_ms" not in d["xgmi"]
+    x = _input("C2", world)
+    assert np.load(tmp_path / "swap.npy").tobytes() == np.ascontiguousarray(x.transpose(1, 2, 0)).tobytes()
+    assert np.allclose(np.load(tmp_path / "mean.npy"), x.astype(np.float64).mean(0), rtol=1e-6, atol=0)
+    assert np.allclose(np.load(tmp_path / "std.npy"), x.astype(np.float64).std(0), rtol=1e-6, atol=0)
+    r = _bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline",
                 "--shapes", SHAPES],
                {"BOLT_AMD_BENCH_BACKEND": "gloo", "BOLT_AMD_BENCH_DEVICE": "cpu"})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -241,13 +281,84 @@ def _find(d, path):
     return d
 
 
-def test_bench_one_rank_rehearsal_record():
-    """The default run's record on one rank (CPU rehearsal): the driver's
+def _plain_one_rank_record(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W`: the contract keys with their
+    meaning (value = the step's algorithmic bytes over ms_per_step), N timed
+    steps and nothing after them; with --dump-outputs the three results of the
+    C2 step as float32, equal to the transposed input / within the float32
+    parity rule of its float64 statistics, byte for byte the same in a second
+    run of other --steps."""
+    d, notes = _plain(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")], {})
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+              "scaling", "dtype", "config", "roofline"):
+        assert k in d, k
+    assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    step_bytes = sum(d["config"]["bytes_per_step"].values())
+    assert step_bytes == 2 * 1024 + 2 * (1024 + 256)
+    # value and ms_per_step are one measurement (both rounded in the record)
+    assert abs(d["value"] - step_bytes / (d["ms_per_step"] / 1e3) / 1e9) <= 0.005 + 0.01 * d["value"]
+    # the run's own progress lines: the timed steps, then the dump, then nothing
+    assert len(notes) == 2 and "C2: 1 warm-up + 3 timed steps" in notes[0] and "writing the last" in notes[1], notes
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["mean.npy", "std.npy", "swap.npy"]
+    assert d["outputs"]["elements"] == {"swap": [256, 256], "mean": [64, 64], "std": [64, 64]}
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    x = _input("C2")
+    assert got["swap"].tobytes() == np.ascontiguousarray(x.transpose(1, 2, 0)).tobytes()
+    assert np.allclose(got["mean"], x.astype(np.float64).mean(0), rtol=1e-6, atol=0)
+    assert np.allclose(got["std"], x.astype(np.float64).std(0), rtol=1e-6, atol=0)
+    d2, _ = _plain(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")], {})
+    assert d2["steps"] == 2
+    for f in files:
+        assert open(tmp_path / "a" / f, "rb").read() == open(tmp_path / "b" / f, "rb").read(), f
+    # every op of another config's step hands its result to the dump: C4's uint16
+    # swap / chunk (packed records) / unchunk exactly as float32, var as float64
+    d, _ = _plain(["--config", "C4", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "c4")], {})
+    assert sorted(os.listdir(tmp_path / "c4")) == ["chunk.npy", "swap.npy", "unchunk.npy", "var.npy"]
+    x = _input("C4").view(np.uint16)
+    swap, unchunk, var = (np.load(tmp_path / "c4" / ("%s.npy" % n)) for n in ("swap", "unchunk", "var"))
+    assert swap.dtype == np.float32 and np.array_equal(swap, x.transpose(1, 0, 2).astype(np.float32))
+    assert np.array_equal(unchunk, x.astype(np.float32))
+    assert np.load(tmp_path / "c4" / "chunk.npy").size == d["outputs"]["elements"]["chunk"][1] >= x.size
+    assert var.dtype == np.float64 and np.allclose(var, x.astype(np.float64).var(0), rtol=1e-12)
+
+
+def _dump_sampling(tmp_path, monkeypatch):
+    """A result over its share of the dump's byte budget is reduced to a fixed
+    seeded sample: sorted flat indices, the same in every call; small results
+    stay whole; wide integers go to float64."""
+    sys.path[:0] = [HERE, ROOT]
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4000)
+    big = np.arange(100000, dtype=np.float32).reshape(100, 1000)
+    kept = [("big", big), ("small", np.arange(10, dtype=np.float64)), ("ints", np.arange(5, dtype=np.int64) << 40)]
+    done = bench.dump_outputs(str(tmp_path / "s1"), kept)
+    bench.dump_outputs(str(tmp_path / "s2"), kept)
+    assert done == {"big": [1000, 100000], "small": [10, 10], "ints": [5, 5]}
+    a = np.load(tmp_path / "s1" / "big.npy")
+    assert a.shape == (1000,) and a.dtype == np.float32 and np.all(np.diff(a) >= 0)
+    assert len(np.unique(a)) > 900 and a.min() < 5000 and a.max() > 95000  # spread over the whole result
+    assert a.tobytes() == np.load(tmp_path / "s2" / "big.npy").tobytes()
+    assert np.load(tmp_path / "s1" / "small.npy").dtype == np.float64
+    ints = np.load(tmp_path / "s1" / "ints.npy")
+    assert ints.dtype == np.float64 and np.array_equal(ints, (np.arange(5, dtype=np.int64) << 40).astype(np.float64))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 3 * 4000 + 3 * 128
+
+
+def test_bench_one_rank_rehearsal_record(tmp_path, monkeypatch):
+    """The plain run's record and its --dump-outputs (_plain_one_rank_record,
+    _dump_sampling), then the default --full run's record on one rank (CPU
+    rehearsal): the driver's
     contract keys, the C2 ops, stats_roofline for mean / std, target64 and the
     C1 / C3 / C4 / C5 sub-records with per-op time, fraction of peak and check;
     and every headline number inside the record's last 7,000 characters (the
     tail the driver keeps), which must parse as JSON from a key on."""
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-pmc", "--no-cpu-baseline", "--target-steps", "1",
+    _plain_one_rank_record(tmp_path)
+    _dump_sampling(tmp_path, monkeypatch)
+    r = _bench(["--steps", "2", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--target-steps", "1",
                 "--shapes", SHAPES], {"BOLT_AMD_BENCH_DEVICE": "cpu"})
     assert r.returncode == 0, r.stderr[-3000:]
     text = r.stdout.strip().splitlines()[-1]
@@ -301,7 +412,7 @@ def test_record_length_budget():
     7,000 characters the driver keeps: a record with every field the GPU run
     fills (PMC traffic ratios, the CPU baseline, wide numbers) is built from
     the rehearsal's and measured."""
-    r = _bench(["--steps", "1", "--warmup", "1", "--no-pmc", "--no-cpu-baseline", "--target-steps", "1",
+    r = _bench(["--steps", "1", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline", "--target-steps", "1",
                 "--config-steps", "1", "--shapes", SHAPES], {"BOLT_AMD_BENCH_DEVICE": "cpu"})
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -361,15 +472,16 @@ def test_rocprof_windows_on_a_synthetic_trace():
 
 
 def test_rocprof_only_on_gpu_ranks(monkeypatch):
-    """rank 0 goes under rocprofv3 only in an N-rank GPU run (never on one
+    """rank 0 goes under rocprofv3 only in an N-rank --full GPU run (never on one
     rank, on the CPU rehearsal, with --no-rocprof or BOLT_AMD_BENCH_ROCPROF=0)."""
     sys.path.insert(0, ROOT)
     import bench
     monkeypatch.setattr(bench, "rocprof_path", lambda: "/opt/rocm/bin/rocprofv3")
-    a = bench.parse(["--gpus", "2"])
+    a = bench.parse(["--gpus", "2", "--full"])
     assert bench.rocprof_wanted(a, 2, "0") and not bench.rocprof_wanted(a, 1, "0")
     assert not bench.rocprof_wanted(a, 2, "cpu")
-    assert not bench.rocprof_wanted(bench.parse(["--no-rocprof"]), 2, "0")
+    assert not bench.rocprof_wanted(bench.parse(["--gpus", "2"]), 2, "0")  # a plain run is not profiled
+    assert not bench.rocprof_wanted(bench.parse(["--full", "--no-rocprof"]), 2, "0")
     monkeypatch.setenv("BOLT_AMD_BENCH_ROCPROF", "0")
     assert not bench.rocprof_wanted(a, 2, "0")
 

@@ -9,7 +9,8 @@ gather's hipEvent times, and the buffers' addresses -- the copy is the
 placement's own ceiling, so gather / copy separates the kernel from the
 pages it was handed.
 
-    python tools/c5_place_bench.py [bench.py args ...] > out.json 2> err.log
+    python tools/c5_place_bench.py --full [bench.py args ...] > out.json 2> err.log
+(--full: the C5 sub-record, "the later ops and checks", belongs to the full run.)
 Prints one JSON line per large gather on stderr (prefix "GATHER ") and
 bench.py's own line on stdout.
 """

@@ -7,6 +7,8 @@
 set -o pipefail
 export TMPDIR=/tmp
 T=${TAG:-r05g}
+OUT=${OUT:-run_out}
+mkdir -p $OUT
 SHAPES=${SHAPES:-'{"C1":[100,64,64],"C2":[200,512,512],"C3":[256,256,256,32],"C4":[800,1024,1024],"C5":[16,64,64,64,64]}'}
 for n in ${NS:-2 4}; do
   echo "[$(date +%T)] $n ranks"
@@ -17,8 +19,8 @@ for n in ${NS:-2 4}; do
   else
     L="python"
   fi
-  BOLT_AMD_BENCH_BACKEND=gloo BOLT_AMD_BENCH_DEVICE=0 timeout -k 10 600 $L bench.py --gpus $n --steps 3 --warmup 1 --shapes "$SHAPES" --detail gpurun_out/${T}_n${n}_detail.json > gpurun_out/${T}_n${n}_rehearsal.json 2> gpurun_out/${T}_n${n}_rehearsal.err || { echo REHEARSAL_FAIL $n; tail -30 gpurun_out/${T}_n${n}_rehearsal.err; exit 1; }
-  python - gpurun_out/${T}_n${n}_rehearsal.json <<'PY'
+  BOLT_AMD_BENCH_BACKEND=gloo BOLT_AMD_BENCH_DEVICE=0 timeout -k 10 600 $L bench.py --gpus $n --steps 3 --warmup 1 --full --shapes "$SHAPES" --detail $OUT/${T}_n${n}_detail.json > $OUT/${T}_n${n}_rehearsal.json 2> $OUT/${T}_n${n}_rehearsal.err || { echo REHEARSAL_FAIL $n; tail -30 $OUT/${T}_n${n}_rehearsal.err; exit 1; }
+  python - $OUT/${T}_n${n}_rehearsal.json <<'PY'
 import json, sys
 d = json.loads([ln for ln in open(sys.argv[1]).read().splitlines() if ln.startswith("{")][-1])
 print("n_gpus", d["n_gpus"], "exchange_check", d.get("exchange_check"), "launcher", d.get("launcher"), "chars", len(json.dumps(d, separators=(",", ":"))))
