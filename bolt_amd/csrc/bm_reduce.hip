@@ -376,24 +376,35 @@ __device__ __forceinline__ double finish(int stat, double mean, double m2, doubl
 }
 
 // Output sink: either final values or state planes (p0, p1) at index e.
+constexpr int kFinalMoments = 2;  // final_out: mean / var / std planes, each optional (bm_reduce_moments)
 struct Sink {
-  void *out;        // final output (final_out != 0)
+  void *out;        // final output (final_out == 1)
   int out_dtype;
   int stat;
-  int final_out;
+  int final_out;    // 0: state planes, 1: `out`, kFinalMoments: om / ov / os
   double *p0;       // state plane 0 (mean / fsum) or uint64 plane (isum / or)
   double *p1;       // state plane 1 (M2)
   double *p2;       // var / std chunk partials: the row's pivot P per output
   int shifted;      // var / std: p0 holds mean - P (chunk partials in the workspace)
+  void *om, *ov, *os;  // kFinalMoments: mean / var / std outputs (NULL: not asked for)
 };
 
 // var / std output of one (output, chunk): the Welford state is kept around
 // the pivot P (an element of the output's first row), mean_y = mean - P.
-// Final: var / std (M2 only); state: mean, M2 -- shifted for the workspace
+// Final: var / std (M2 only), or every moment asked for from the one state
+// (the StatCounter of statcounter.py:30-48 holds n, mu and m2 together: mean
+// = P + mean_y, var = M2 / n, std = sqrt(var), the var / std arithmetic of
+// the single-statistic sink); state: mean, M2 -- shifted for the workspace
 // partials (chunk 0 records P), absolute for bm_reduce_state.
 __device__ __forceinline__ void emit_mom(const Sink &sk, int64_t idx, int64_t e, int64_t c, double n,
                                          double mean_y, double m2, double P) {
   m2 = m2 > 0.0 ? m2 : 0.0;
+  if (sk.final_out == kFinalMoments) {
+    if (sk.om) store_out(sk.om, idx, n > 0.0 ? P + mean_y : 0.0, sk.out_dtype);
+    if (sk.ov) store_out(sk.ov, idx, finish(BM_STAT_VAR, 0.0, m2, n), sk.out_dtype);
+    if (sk.os) store_out(sk.os, idx, finish(BM_STAT_STD, 0.0, m2, n), sk.out_dtype);
+    return;
+  }
   if (sk.final_out) {
     store_out(sk.out, idx, finish(sk.stat, 0.0, m2, n), sk.out_dtype);
     return;
@@ -1605,6 +1616,40 @@ extern "C" int bm_reduce_rows(int stat, const void *src, int in_dtype, int64_t O
                        stream, "bm_reduce_rows");
 }
 
+// mean, var and std of one pass: BM_STAT_VAR's plan, workspace and launches
+// (plan_reduce does not look at the statistic), the last store writing every
+// moment asked for instead of one.
+extern "C" int bm_reduce_moments(const void *src, int in_dtype, int64_t O, int64_t R, int64_t I,
+                                 int64_t row_pitch, void *out_mean, void *out_var, void *out_std,
+                                 int out_dtype, void *workspace, size_t workspace_bytes, void *stream) {
+  const char *who = "bm_reduce_moments";
+  int rc = check_args(BM_STAT_VAR, in_dtype, O, R, I, who);
+  if (rc) return rc;
+  if (!src) { bm_set_error("%s: null pointer", who); return BM_E_ARG; }
+  if (!out_mean && !out_var && !out_std) {
+    bm_set_error("%s: no output asked for (out_mean, out_var and out_std are all null)", who);
+    return BM_E_ARG;
+  }
+  if (!is_float(out_dtype)) {
+    bm_set_error("%s: out_dtype %d is not a float dtype", who, out_dtype);
+    return BM_E_ARG;
+  }
+  if (row_pitch < R || (I > 1 && row_pitch != R)) {
+    bm_set_error("%s: row_pitch %lld does not fit R=%lld, I=%lld (>= R, and R itself unless I == 1)", who,
+                 (long long)row_pitch, (long long)R, (long long)I);
+    return BM_E_ARG;
+  }
+  Sink sk{};
+  sk.out_dtype = out_dtype;
+  sk.stat = BM_STAT_VAR;
+  sk.final_out = kFinalMoments;
+  sk.om = out_mean;
+  sk.ov = out_var;
+  sk.os = out_std;
+  return run_reduce(BM_STAT_VAR, src, in_dtype, O, R, I, sk, workspace, workspace_bytes,
+                    (hipStream_t)stream, who, row_pitch);
+}
+
 extern "C" int bm_reduce_state_bytes(int stat, int in_dtype, int64_t nout, size_t *bytes) {
   if (!bytes || nout < 0 || stat < BM_STAT_MEAN || stat > BM_STAT_FMIN || dtype_size(in_dtype) == 0) {
     bm_set_error("bm_reduce_state_bytes: bad arguments");
@@ -1665,4 +1710,36 @@ extern "C" int bm_reduce_combine(int stat, int in_dtype, const void *states, con
   int rc = launch_combine(mode, in_dtype, p0, p0 + nout, cd, sk, (hipStream_t)stream);
   if (rc) return rc;
   return check_launch("bm_reduce_combine");
+}
+
+// bm_reduce_combine(BM_STAT_VAR, ...)'s merge, finalised into every moment asked for.
+extern "C" int bm_reduce_combine_moments(int in_dtype, const void *states, const int64_t *counts, int nparts,
+                                         int64_t nout, void *out_mean, void *out_var, void *out_std,
+                                         int out_dtype, void *stream) {
+  if (dtype_size(in_dtype) == 0 || nparts < 1 || nparts > kMaxParts || nout < 1 || !states || !counts ||
+      (!out_mean && !out_var && !out_std)) {
+    bm_set_error("bm_reduce_combine_moments: bad arguments");
+    return BM_E_ARG;
+  }
+  if (!is_float(out_dtype)) {
+    bm_set_error("bm_reduce_combine_moments: out_dtype %d is not a float dtype", out_dtype);
+    return BM_E_ARG;
+  }
+  CombDesc cd{};
+  cd.nout = nout;
+  cd.nparts = nparts;
+  cd.part_stride = (int64_t)planes_of(M_MOM) * nout;
+  cd.explicit_counts = 1;
+  for (int p = 0; p < nparts; ++p) cd.counts[p] = counts[p];
+  Sink sk{};
+  sk.out_dtype = out_dtype;
+  sk.stat = BM_STAT_VAR;
+  sk.final_out = kFinalMoments;
+  sk.om = out_mean;
+  sk.ov = out_var;
+  sk.os = out_std;
+  const double *p0 = (const double *)states;
+  int rc = launch_combine(M_MOM, in_dtype, p0, p0 + nout, cd, sk, (hipStream_t)stream);
+  if (rc) return rc;
+  return check_launch("bm_reduce_combine_moments");
 }

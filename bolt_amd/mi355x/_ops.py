@@ -320,6 +320,17 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_reduce_rows")
 
+    def reduce_moments(self, src, code, O, R, I, pitch, outs, out_code):
+        """mean / var / std of one read of ``src`` ([O][R][I]; rows ``pitch``
+        elements apart when I == 1): ``outs`` = (mean, var, std) tensors, None
+        for a moment not asked for."""
+        ws, nws = self._workspace(_lib.STAT_VAR, code, O, R, I, src.device)
+        om, ov, os_ = (o.data_ptr() if o is not None else None for o in outs)
+        rc = self.lib.bm_reduce_moments(src.data_ptr(), code, O, R, I, pitch, om, ov, os_, out_code,
+                                        ws.data_ptr() if ws is not None else None, nws, raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_reduce_moments")
+
     def state_bytes(self, stat, code, nout):
         n = ctypes.c_size_t(0)
         _lib.check(self.lib.bm_reduce_state_bytes(stat, code, nout, ctypes.byref(n)), "bm_reduce_state_bytes")
@@ -335,6 +346,13 @@ class HipBackend(object):
         _lib.check(self.lib.bm_reduce_combine(stat, code, self._ptr(states), _lib.i64_array(counts),
                                               len(counts), nout, self._ptr(out), out_code,
                                               self._stream(states)), "bm_reduce_combine")
+
+    def reduce_combine_moments(self, code, states, counts, nout, outs, out_code):
+        """reduce_combine of STAT_VAR states into ``outs`` = (mean, var, std) tensors (None: not asked for)."""
+        om, ov, os_ = (self._ptr(o) if o is not None else None for o in outs)
+        _lib.check(self.lib.bm_reduce_combine_moments(code, self._ptr(states), _lib.i64_array(counts),
+                                                      len(counts), nout, om, ov, os_, out_code,
+                                                      self._stream(states)), "bm_reduce_combine_moments")
 
 
 _BACKENDS = {}

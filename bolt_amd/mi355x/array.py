@@ -14,8 +14,12 @@ Operations and what replaces the Spark machinery:
   sum / mean / var / std: one reduction kernel over the aligned layout
       (array.py:243-395 + statcounter.py), float64 accumulation; across GPUs
       per-rank states -> all_gather -> ordered Chan combine.
+  stats: several of mean / var / std from ONE read (the StatCounter's
+      stats='all', statcounter.py:30-48): the variance's launch sequence
+      storing every moment asked for (bm_reduce_moments).
   toarray / tolocal: D2H (+ all_gather of the slabs).
 """
+import collections
 import functools
 import os
 
@@ -26,7 +30,7 @@ from bolt_amd.mi355x._ops import backend_for, dtype_code
 from bolt_amd.base import BoltArray
 from bolt_amd.mi355x.context import local_shape
 from bolt_amd.mi355x.dist import all_gather_bytes, concat_rows_sharded, gather_to_host, permute_sharded, redistribute_rows, select_sharded, _empty
-from bolt_amd.mi355x.transfer import finish_host_result, host_result, to_device, to_host
+from bolt_amd.mi355x.transfer import SMALL as HOST_RESULT_MAX, finish_host_result, host_result, to_device, to_host
 from bolt_amd.local import BoltArrayLocal
 from bolt_amd.mi355x.plan import getplan, check_plan, padded_strides, swap_perm, swap_shape, reduce_layout, stat_dtype
 from bolt_amd.utils import tupleize, argpack, inshape, istransposeable, isreshapeable
@@ -205,7 +209,85 @@ def _aligned_vshape_of(shape, split, axis):
 
 
 _REDUCE_PLANS = {}  # (local shape, axes, stat, dtype, world) -> device reduction plan
+_MOMENT_PLANS = {}  # (local shape, axes, dtype, shape, world) -> device plan of stats() (one read, several moments)
+
+# stats(): one StatCounter pass read for several moments (statcounter.py:30-48)
+Stats = collections.namedtuple('Stats', ('count', 'mean', 'var', 'std'))
+_STATS_FIELDS = ('mean', 'var', 'std')  # the order of bm_reduce_moments' outputs
+_STATS_NAMES = {'mean': 'mean', 'var': 'var', 'variance': 'var', 'std': 'std', 'stdev': 'std'}
 _STAT_AXES = {}  # (shape, split, axis as given) -> (validated axes, records after _align, record shape | None)
+
+
+def _moment_planes(be, dev, out_dtype, want, n, launch, host_ok):
+    """One buffer of a plane of ``n`` values per moment of ``want``, filled by
+    ``launch((mean, var, std) tensors, None where not asked for)``: page-locked
+    host memory when the kernels can store into it (``host_ok``: one rank), else
+    HBM.  -> (host ndarray (len(want), n), or a list of its rows, after one
+    stream synchronise, None) or (None, device buffer)."""
+    nb = n * out_dtype.itemsize
+    host = host_result(be, len(want) * nb, dev) if host_ok else None
+    if host is None and host_ok and nb <= HOST_RESULT_MAX < len(want) * nb:
+        # the planes together pass the zero-copy limit, each alone does not
+        # (C4's 8 MiB float64 planes): a page-locked buffer per plane, as the
+        # single statistics get -- a staged D2H of the planes cost 0.76 ms
+        # there, more than the saved read (profiles/stats_fused_ab.log)
+        hosts = [host_result(be, nb, dev) for _ in want]
+        if all(h is not None for h in hosts):
+            outs = [None, None, None]
+            for h, f in zip(hosts, want):
+                outs[_STATS_FIELDS.index(f)] = h
+            launch(tuple(outs))
+            first = finish_host_result(hosts[0], dev, out_dtype, (n,))
+            return [first] + [h.numpy().view(out_dtype) for h in hosts[1:]], None
+    buf = host if host is not None else _empty(len(want) * nb, dev)
+    outs = [None, None, None]
+    for j, f in enumerate(want):
+        outs[_STATS_FIELDS.index(f)] = buf[j * nb:(j + 1) * nb]
+    launch(tuple(outs))
+    if host is not None:
+        return finish_host_result(host, dev, out_dtype, (len(want), n)), None
+    return None, buf
+
+
+def _combine_moments(be, code, ocode, out_dtype, want, states, counts, nout, host_ok):
+    """STAT_VAR states of ``len(counts)`` parts -> _moment_planes' result."""
+    if hasattr(be, "reduce_combine_moments"):
+        return _moment_planes(be, states.device, out_dtype, want, nout,
+                              lambda outs: be.reduce_combine_moments(code, states, counts, nout, outs, ocode),
+                              host_ok)
+
+    def per_field(outs):
+        # an executor without the fused entry points (the CPU test executor):
+        # the same states merged once per moment; the mean's merge takes the
+        # one-plane STAT_MEAN layout (the mean planes, part-major)
+        om, ov, osd = outs
+        with np.errstate(all="ignore"):  # a numpy executor on pad columns' unwritten values (dropped later)
+            if om is not None:
+                means = states.view(len(counts), 2, nout * 8)[:, 0, :].contiguous().view(-1)
+                be.reduce_combine(_lib.STAT_MEAN, code, means, counts, nout, om, ocode)
+            if ov is not None:
+                be.reduce_combine(_lib.STAT_VAR, code, states, counts, nout, ov, ocode)
+            if osd is not None:
+                be.reduce_combine(_lib.STAT_STD, code, states, counts, nout, osd, ocode)
+    return _moment_planes(be, states.device, out_dtype, want, nout, per_field, host_ok)
+
+
+def _launch_moments(be, src, es, code, ocode, out_dtype, want, O, R, I, pitch, host_ok):
+    """The moments ``want`` of one read of ``src`` ([O][R][I] elements of ``es``
+    bytes, rows ``pitch`` elements apart when I == 1) -> _moment_planes' result."""
+    if hasattr(be, "reduce_moments"):
+        return _moment_planes(be, src.device, out_dtype, want, O * I,
+                              lambda outs: be.reduce_moments(src, code, O, R, I, pitch, outs, ocode), host_ok)
+    # an executor without the fused entry points: still one read, into a
+    # STAT_VAR state that every moment is finalised from
+    if pitch != R:
+        dense = _empty(O * R * es, src.device)
+        be.copy_strided(src, 0, dense, 0, [O, R], [pitch, 1], [R, 1], es)
+        src = dense
+    state = _empty(be.state_bytes(_lib.STAT_VAR, code, O * I), src.device)
+    with np.errstate(all="ignore"):  # pad columns' unwritten values, as in _combine_moments
+        be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
+    return _combine_moments(be, code, ocode, out_dtype, want, state, [R], O * I, host_ok)
 
 
 class BoltArrayMI355X(BoltArray):
@@ -1169,6 +1251,185 @@ class BoltArrayMI355X(BoltArray):
             if stat == _lib.STAT_STD:
                 v = np.sqrt(v)
         return np.asarray(v, dtype=np.float64).astype(out_dtype).reshape(out_shape)
+
+    def _reduced_moments(self, axis, want):
+        """_reduced for several moments of one read: ``want`` is a subset of
+        ('mean', 'var', 'std') in that order -> {field: host ndarray with the
+        kept axes (ascending)}.  The layouts are _reduced's, branch for branch;
+        the data is read by one STAT_VAR launch sequence (bm_reduce_moments),
+        so var and std carry the bits of their own methods."""
+        ctx = self._ctx
+        lshape = self._local_shape
+        pkey = (lshape, tuple(axis), self._dtype, self._shape, ctx.world_size)
+        plan = _MOMENT_PLANS.get(pkey)
+        if plan is None:
+            axset = sorted(set(int(a) for a in axis))
+            kept = [i for i in range(self.ndim) if i not in axset]
+            out_shape = tuple(self._shape[i] for i in kept)
+            out_dtype = stat_dtype(self._dtype, out_shape)
+            perm, O, R, I = reduce_layout(lshape, axset)
+            loc_out = tuple(lshape[i] for i in kept)
+            plan = (axset, out_shape, out_dtype, dtype_code(self._dtype), dtype_code(out_dtype),
+                    perm, O, R, I, int(np.prod(lshape, dtype=np.int64)), int(np.prod(loc_out, dtype=np.int64)))
+            if len(_MOMENT_PLANS) > 4096:
+                _MOMENT_PLANS.clear()
+            _MOMENT_PLANS[pkey] = plan
+        axset, out_shape, out_dtype, code, ocode, perm, O, R, I, nloc, nout = plan
+        k = len(want)
+        es = self._dtype.itemsize
+        pbuf = self.__dict__.get("_pbuf")
+        single = ctx.world_size == 1
+
+        def fields(planes):
+            return dict((f, planes[j].reshape(out_shape)) for j, f in enumerate(want))
+
+        def gathered(buf):
+            # per-rank (k, this rank's outputs) planes -> (k, every output)
+            isz = out_dtype.itemsize
+            sizes = [k * int(np.prod((hi - lo,) + out_shape[1:], dtype=np.int64)) * isz
+                     for lo, hi in ctx.bounds(self._shape[0])]
+            flat = to_host(all_gather_bytes(ctx, buf, sizes), out_dtype, (-1,))
+            parts, off = [], 0
+            for s in sizes:
+                n = s // isz
+                parts.append(flat[off:off + n].reshape(k, n // k))
+                off += n
+            return np.concatenate(parts, axis=1)
+
+        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and not single and 0 not in axset:
+            # last-axis statistics of a row-padded slab, read in place, then gathered
+            be = backend_for(pbuf.device)
+            if nout and nloc:
+                _, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, 1, self._pitch, False)
+            else:
+                buf = _empty(0, pbuf.device)
+            return fields(gathered(buf))
+        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and nloc and single:
+            # last-axis statistics of a row-padded array: the rows read in place
+            be = backend_for(pbuf.device)
+            host, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, 1, self._pitch, True)
+            return fields(host if host is not None else to_host(buf, out_dtype, (k, nout)))
+        if pbuf is not None and perm is None and I > 1 and I % lshape[-1] == 0 and nloc and single:
+            # leading / middle axes of a row-padded array: columns over the
+            # padded rows, the pad columns' outputs dropped (see _reduced)
+            be = backend_for(pbuf.device)
+            Rl, P = lshape[-1], self._pitch
+            Ip = I // Rl * P
+            host, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, Ip, R, True)
+            full = host if host is not None else to_host(buf, out_dtype, (k, O * Ip))
+            return dict((f, np.ascontiguousarray(full[j].reshape(O, I // Rl, P)[:, :, :Rl]).reshape(out_shape))
+                        for j, f in enumerate(want))
+        if pbuf is not None and perm is None and O == 1 and I == 1 and R == nloc and nloc \
+                and single and len(lshape) >= 2 and self._dtype.kind == "f" and self._dtype.itemsize >= 4:
+            # every axis of a row-padded float array: the one column state of
+            # _padded_all_moments holds the mean and M2 of every moment
+            be = backend_for(pbuf.device)
+            Rl, P = lshape[-1], self._pitch
+            nrows = nloc // Rl
+            state = _empty(be.state_bytes(_lib.STAT_VAR, code, P), pbuf.device)
+            be.reduce_state(_lib.STAT_VAR, pbuf, code, 1, nrows, P, state)
+            planes = to_host(state, np.float64, (-1, P))
+            means = planes[0, :Rl]
+            mean = means.mean()
+            var = (planes[1, :Rl].sum() + nrows * np.square(means - mean).sum()) / (nrows * Rl)
+            vals = {'mean': mean, 'var': var, 'std': np.sqrt(var)}
+            return dict((f, np.asarray(vals[f], dtype=np.float64).astype(out_dtype).reshape(out_shape))
+                        for f in want)
+        be = self._backend
+        dev = self._device
+        if perm is not None:
+            # the reduced axes first (_align's swap), once for every moment
+            tmp = _empty(nloc * es, dev)
+            if pbuf is not None:
+                pstr = _padded_strides(lshape, self._pitch)
+                pshape = [lshape[p] for p in perm]
+                be.copy_strided(pbuf, 0, tmp, 0, pshape, [pstr[p] for p in perm],
+                                _padded_strides(pshape, pshape[-1]), es)
+            elif nloc:
+                be.permute(self._data, lshape, perm, es, tmp)
+            src = tmp
+        else:
+            src = self._data
+
+        if single or 0 not in axset:
+            # every output lives on this rank (or this rank's slab of them)
+            if nout and nloc:
+                host, buf = _launch_moments(be, src, es, code, ocode, out_dtype, want, O, R, I, R, single)
+            else:
+                host, buf = None, _empty(0, dev)
+            if not single:
+                return fields(gathered(buf))
+            return fields(host if host is not None else to_host(buf, out_dtype, (k, nout)))
+
+        # the sharded axis is reduced: one STAT_VAR state per rank, gathered
+        # once and merged in rank order into every moment
+        nout = int(np.prod(out_shape, dtype=np.int64))
+        if nout == 0:
+            return dict((f, np.empty(out_shape, out_dtype)) for f in want)
+        if ctx.world_size > _lib.MAX_COMBINE_PARTS:
+            raise NotImplementedError("reductions over the sharded axis merge at most %d ranks (got %d)"
+                                      % (_lib.MAX_COMBINE_PARTS, ctx.world_size))
+        sbytes = be.state_bytes(_lib.STAT_VAR, code, nout)
+        state = _empty(sbytes, dev)
+        if int(np.prod([lshape[i] for i in axset], dtype=np.int64)):
+            be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
+        else:
+            state.zero_()
+        counts = [(hi - lo) * int(np.prod([self._shape[i] for i in axset if i != 0], dtype=np.int64))
+                  for lo, hi in ctx.bounds(self._shape[0])]
+        states = all_gather_bytes(ctx, state, [sbytes] * ctx.world_size)
+        _, buf = _combine_moments(be, code, ocode, out_dtype, want, states, counts, nout, False)
+        return fields(to_host(buf, out_dtype, (k, nout)))
+
+    def stats(self, axis=None, keepdims=False, names=_STATS_FIELDS):
+        """Several moments over ``axis`` from one read of the array: the
+        reference's StatCounter (statcounter.py:30-48, stats='all') holds the
+        count, mean and M2 of one pass, of which _stat (array.py:284-334)
+        reads one per call.  An addition to the reference's API.
+
+        ``names``: a non-empty subset of 'mean', 'var', 'std' (one string, or
+        the reference's spellings 'variance' / 'stdev').  Returns a ``Stats``
+        namedtuple (count, mean, var, std): count is the number of records
+        reduced per output; each field asked for is what its method returns
+        (var and std bit for bit, the mean within rounding: it is the Welford
+        mean of the variance's state), the others None.
+        """
+        if isinstance(names, str):
+            names = (names,)
+        try:
+            asked = set(_STATS_NAMES[n] for n in names)
+        except (KeyError, TypeError):
+            raise ValueError("stats: names must be among %s, got %r" % (sorted(_STATS_NAMES), names))
+        if not asked:
+            raise ValueError("stats: no statistic asked for")
+        want = tuple(f for f in _STATS_FIELDS if f in asked)
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        count = self._nrecords(ax)
+        if len(want) == 1:
+            one = getattr(self, want[0])(axis=axis, keepdims=keepdims)
+            return Stats(count=count, **dict((f, one if f == want[0] else None) for f in _STATS_FIELDS))
+        if count == 0:
+            # the empty StatCounter, as _stat gives it: mean 0.0, variance / stdev nan
+            res = dict((f, 0.0 if f == 'mean' else float('nan')) for f in want)
+        else:
+            vs = self._aligned_vshape(ax)
+            res = self._reduced_moments(ax, want)
+            for f in want:
+                arr = res[f]
+                if vs is not None:
+                    arr = arr.reshape(vs)
+                if arr.ndim == 0:
+                    arr = arr[()]
+                res[f] = arr
+        out = dict.fromkeys(_STATS_FIELDS)
+        for f in want:
+            arr = res[f]
+            if keepdims:
+                for i in ax:
+                    arr = np.expand_dims(arr, axis=i)
+            out[f] = BoltArrayLocal(arr).toscalar()
+        return Stats(count=count, **out)
 
     def _stat(self, axis=None, func=None, name=None, keepdims=False):
         """Statistic over ``axis`` (array.py:284-334); results are host arrays / scalars."""

@@ -266,6 +266,25 @@ int bm_reduce_rows(int stat, const void *src, int in_dtype, int64_t O, int64_t R
                    size_t workspace_bytes, void *stream);
 
 /*
+ * bm_reduce_moments -- mean, variance and standard deviation of one read of
+ * src: what the reference's StatCounter holds after one pass over a partition
+ * (stats='all': n, mu and m2 together, bolt/spark/statcounter.py:30-48), which
+ * _stat (bolt/spark/array.py:284-334) reads one moment of per call.  The
+ * layout is bm_reduce's [O][R][I]; with I == 1, row_pitch >= R reads padded
+ * rows as bm_reduce_rows does (row_pitch = R otherwise).  out_mean / out_var /
+ * out_std receive O*I values of out_dtype (a float dtype) each; any may be
+ * NULL (not all), and any may be a bm_host_writable host buffer.  The launches,
+ * workspace (bm_reduce_workspace_bytes of BM_STAT_VAR) and summation order are
+ * those of bm_reduce(BM_STAT_VAR): var and std are bit-identical to
+ * bm_reduce's, the mean is the Welford mean of the same state (S1 / n for 1-
+ * and 2-byte integers), within rounding of bm_reduce(BM_STAT_MEAN)'s.
+ */
+int bm_reduce_moments(const void *src, int in_dtype, int64_t O, int64_t R,
+                      int64_t I, int64_t row_pitch, void *out_mean, void *out_var,
+                      void *out_std, int out_dtype, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
+/*
  * Partial reduction state for the multi-GPU merge (the per-partition
  * StatCounter of array.py:321-322).  `state` receives, for O*I outputs:
  *   MEAN/VAR/STD: two float64 planes, mean[O*I] then M2[O*I] (count = R);
@@ -290,6 +309,21 @@ int bm_reduce_state(int stat, const void *src, int in_dtype, int64_t O,
 int bm_reduce_combine(int stat, int in_dtype, const void *states,
                       const int64_t *counts, int nparts, int64_t nout,
                       void *out, int out_dtype, void *stream);
+
+/*
+ * bm_reduce_combine(BM_STAT_VAR) finalised into every moment asked for: the
+ * merged StatCounter (bolt/spark/statcounter.py:30-48, :67-99) read for mean,
+ * variance and stdev at once instead of once per _stat call
+ * (bolt/spark/array.py:284-334).  states: nparts two-plane BM_STAT_VAR states
+ * of bm_reduce_state (mean[nout] then M2[nout], part-major), merged in part
+ * order exactly as bm_reduce_combine merges them.  out_mean / out_var /
+ * out_std as for bm_reduce_moments; with every count 0 the mean is 0 and var /
+ * std are NaN.
+ */
+int bm_reduce_combine_moments(int in_dtype, const void *states,
+                              const int64_t *counts, int nparts, int64_t nout,
+                              void *out_mean, void *out_var, void *out_std,
+                              int out_dtype, void *stream);
 
 /*
  * ---------------------------------------------------------------------------
