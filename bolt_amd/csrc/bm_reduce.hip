@@ -66,8 +66,14 @@ constexpr int kIntUnroll = 8;
 
 enum Mode {
   M_MEAN = 0, M_MOM = 1, M_FSUM = 2, M_ISUM = 3, M_OR = 4, M_MAX = 5, M_MIN = 6,
-  M_FPROD = 7, M_IPROD = 8, M_LAND = 9, M_BAND = 10, M_BOR = 11, M_BXOR = 12, M_FMAX = 13, M_FMIN = 14
+  M_FPROD = 7, M_IPROD = 8, M_LAND = 9, M_BAND = 10, M_BOR = 11, M_BXOR = 12, M_FMAX = 13, M_FMIN = 14,
+  // mean into `out` and the var / std state into the kept planes from one read
+  // (bm_reduce_keep): M_MEAN's and M_MOM's accumulations side by side on the
+  // same loaded registers, each with its own arithmetic and order
+  M_MEANMOM = 15
 };
+template <int MODE> constexpr bool mean_part() { return MODE == M_MEAN || MODE == M_MEANMOM; }
+template <int MODE> constexpr bool mom_part() { return MODE == M_MOM || MODE == M_MEANMOM; }
 
 // "bit modes" keep a uint64 accumulator: modular integer sum / product,
 // logical OR (bool sum, logical_or) / AND, bitwise and / or / xor, and
@@ -387,7 +393,14 @@ struct Sink {
   double *p2;       // var / std chunk partials: the row's pivot P per output
   int shifted;      // var / std: p0 holds mean - P (chunk partials in the workspace)
   void *om, *ov, *os;  // kFinalMoments: mean / var / std outputs (NULL: not asked for)
+  double *k0, *k1;  // bm_reduce_keep: the BM_STAT_VAR state (absolute mean, M2) next to `out` (NULL: not kept)
 };
+
+// the kept copy of the var / std state of output idx: bm_reduce_state's values
+__device__ __forceinline__ void emit_kept(const Sink &sk, int64_t idx, double mean_y, double m2, double P) {
+  sk.k0[idx] = P + mean_y;
+  sk.k1[idx] = m2 > 0.0 ? m2 : 0.0;
+}
 
 // var / std output of one (output, chunk): the Welford state is kept around
 // the pivot P (an element of the output's first row), mean_y = mean - P.
@@ -399,6 +412,7 @@ struct Sink {
 __device__ __forceinline__ void emit_mom(const Sink &sk, int64_t idx, int64_t e, int64_t c, double n,
                                          double mean_y, double m2, double P) {
   m2 = m2 > 0.0 ? m2 : 0.0;
+  if (sk.k0) emit_kept(sk, idx, mean_y, m2, P);
   if (sk.final_out == kFinalMoments) {
     if (sk.om) store_out(sk.om, idx, n > 0.0 ? P + mean_y : 0.0, sk.out_dtype);
     if (sk.ov) store_out(sk.ov, idx, finish(BM_STAT_VAR, 0.0, m2, n), sk.out_dtype);
@@ -496,11 +510,16 @@ __global__ void __launch_bounds__(kThreads)
   if (active) {
     const T *base = src + ((int64_t)o * d.R) * d.I + col0;
     int64_t r = r_lo + ph;
-    if (MODE == M_MOM) {
+    if (mom_part<MODE>()) {
       T p0v[VEC];
       vload<T, VEC>(base, p0v);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) P[k] = to_f64(p0v[k]);
+    }
+    if (MODE == M_MEANMOM) {
+      // never chunked (r_lo == 0): the mean's pivot, the chunk's first row, is P
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k].pivot(P[k]);
     }
     if (MODE == M_MEAN) {
       // one pivot per column for every row phase of the block (the chunk's
@@ -510,13 +529,13 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k].pivot(to_f64(k0[k]));
     }
-    if constexpr (MODE == M_MEAN || MODE == M_MOM || facc_mode<MODE>()) {
+    if constexpr (mean_part<MODE>() || MODE == M_MOM || facc_mode<MODE>()) {
       // kColsUnroll rows in flight per lane; the adds stay in row order
       for (; r + (kColsUnroll - 1) * nph < r_hi; r += kColsUnroll * nph) {
         T v[kColsUnroll][VEC];
 #pragma unroll
         for (int u = 0; u < kColsUnroll; ++u) vload_nt<T, VEC>(base + (r + u * nph) * d.I, v[u]);
-        if constexpr (MODE == M_MOM) {
+        if constexpr (mom_part<MODE>()) {
           // one Welford batch of kColsUnroll rows per column
           double f, nf;
           uniform_weights(wkb, (double)kColsUnroll, f, nf);
@@ -525,6 +544,11 @@ __global__ void __launch_bounds__(kThreads)
             double x[kColsUnroll];
 #pragma unroll
             for (int u = 0; u < kColsUnroll; ++u) x[u] = to_f64(v[u][k]);
+            if constexpr (MODE == M_MEANMOM) {
+              // M_MEAN's adds below: each column's sum takes its rows in order
+#pragma unroll
+              for (int u = 0; u < kColsUnroll; ++u) acc[k].add(x[u]);
+            }
             double mb, qb;
             batch_moments<kColsUnroll>(x, P[k], mb, qb);
             merge_batch(wm[k], wq[k], mb, qb, f, nf);
@@ -550,46 +574,48 @@ __global__ void __launch_bounds__(kThreads)
       vload_nt<T, VEC>(base + (r + 2 * nph) * d.I, v2);
       vload_nt<T, VEC>(base + (r + 3 * nph) * d.I, v3);
       double f = 0.0, nf = 0.0;
-      if (MODE == M_MOM) batch_weights(wn, 4.0, f, nf);
+      if (mom_part<MODE>()) batch_weights(wn, 4.0, f, nf);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        if (MODE == M_MOM) {
+        if (mom_part<MODE>()) {
           const double x[4] = {to_f64(v0[k]), to_f64(v1[k]), to_f64(v2[k]), to_f64(v3[k])};
           double mb, qb;
           batch_moments<4>(x, P[k], mb, qb);
           merge_batch(wm[k], wq[k], mb, qb, f, nf);
-        } else if (MODE == M_MEAN) {
+        }
+        if (mean_part<MODE>()) {
           acc[k].add(to_f64(v0[k])); acc[k].add(to_f64(v1[k]));
           acc[k].add(to_f64(v2[k])); acc[k].add(to_f64(v3[k]));
         } else if (facc_mode<MODE>()) {
           fs[k] = fop<MODE>(fs[k], to_f64(v0[k])); fs[k] = fop<MODE>(fs[k], to_f64(v1[k]));
           fs[k] = fop<MODE>(fs[k], to_f64(v2[k])); fs[k] = fop<MODE>(fs[k], to_f64(v3[k]));
-        } else {
+        } else if (!mom_part<MODE>()) {
           us[k] = bop<T, MODE>(us[k], bop<T, MODE>(bop<T, MODE>(belem<T, MODE>(v0[k]), belem<T, MODE>(v1[k])),
                                                    bop<T, MODE>(belem<T, MODE>(v2[k]), belem<T, MODE>(v3[k]))));
         }
       }
-      if (MODE == M_MOM) wn += 4.0;
+      if (mom_part<MODE>()) wn += 4.0;
     }
     for (; r < r_hi; r += nph) {
       T v[VEC];
       vload_nt<T, VEC>(base + r * d.I, v);
-      if (MODE == M_MOM) wn += 1.0;
+      if (mom_part<MODE>()) wn += 1.0;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        if (MODE == M_MOM) {  // Welford's single-value update
+        if (mom_part<MODE>()) {  // Welford's single-value update
           const double x = to_f64(v[k]) - P[k];
           const double delta = x - wm[k];
           wm[k] += delta / wn;
           wq[k] = fma(delta, x - wm[k], wq[k]);
-        } else if (MODE == M_MEAN) acc[k].add(to_f64(v[k]));
+        }
+        if (mean_part<MODE>()) acc[k].add(to_f64(v[k]));
         else if (facc_mode<MODE>()) fs[k] = fop<MODE>(fs[k], to_f64(v[k]));
-        else us[k] = bop<T, MODE>(us[k], belem<T, MODE>(v[k]));
+        else if (!mom_part<MODE>()) us[k] = bop<T, MODE>(us[k], belem<T, MODE>(v[k]));
       }
     }
   }
 
-  if constexpr (MODE == M_MOM) {
+  if constexpr (mom_part<MODE>()) {
     // row phases: Chan merges in a fixed binary tree over the phases (phase
     // p absorbs p + s at stride s), through LDS
     for (int s = 1; s < nph; s <<= 1) {
@@ -614,16 +640,20 @@ __global__ void __launch_bounds__(kThreads)
         }
       }
     }
-    if (ph != 0 || !active) return;
-    const double ntot = (double)(r_hi - r_lo);
-    const int64_t plane = d.O * d.I;
+    if constexpr (MODE == M_MOM) {
+      if (ph != 0 || !active) return;
+      const double ntot = (double)(r_hi - r_lo);
+      const int64_t plane = d.O * d.I;
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const int64_t e = (int64_t)o * d.I + col0 + k;
-      const int64_t idx = sk.final_out ? e : (c * plane + e);
-      emit_mom(sk, idx, e, c, ntot, wm[k], wq[k], P[k]);
+      for (int k = 0; k < VEC; ++k) {
+        const int64_t e = (int64_t)o * d.I + col0 + k;
+        const int64_t idx = sk.final_out ? e : (c * plane + e);
+        emit_mom(sk, idx, e, c, ntot, wm[k], wq[k], P[k]);
+      }
+      return;
     }
-    return;
+    // M_MEANMOM: phase 0 holds the columns' states; the sums below reuse sm0
+    if (nph > 1) __syncthreads();
   }
 
   // other modes: combine the row phases of each column through LDS (phase
@@ -631,7 +661,7 @@ __global__ void __launch_bounds__(kThreads)
   double m_[VEC];
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
-    if (MODE == M_MEAN) m_[k] = acc[k].s1();
+    if (mean_part<MODE>()) m_[k] = acc[k].s1();
     else if (facc_mode<MODE>()) m_[k] = fs[k];
     else m_[k] = __builtin_bit_cast(double, us[k]);
   }
@@ -645,7 +675,7 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           const double mb = sm0[other * VEC + k];
-          if (MODE == M_MEAN || facc_mode<MODE>()) {
+          if (mean_part<MODE>() || facc_mode<MODE>()) {
             m_[k] = fop<MODE>(m_[k], mb);
           } else {
             m_[k] = __builtin_bit_cast(double, bop<T, MODE>(__builtin_bit_cast(uint64_t, m_[k]),
@@ -660,10 +690,11 @@ __global__ void __launch_bounds__(kThreads)
   const int64_t plane = d.O * d.I;
 #pragma unroll
   for (int k = 0; k < VEC; ++k) {
-    if (MODE == M_MEAN) m_[k] = mean_from_sums(ntot, acc[k].K, m_[k]);
+    if (mean_part<MODE>()) m_[k] = mean_from_sums(ntot, acc[k].K, m_[k]);
     const int64_t e = (int64_t)o * d.I + col0 + k;
     const int64_t idx = sk.final_out ? e : (c * plane + e);
     emit<MODE>(sk, idx, ntot, m_[k], 0.0, __builtin_bit_cast(uint64_t, m_[k]));
+    if constexpr (MODE == M_MEANMOM) emit_kept(sk, idx, wm[k], wq[k], P[k]);
   }
 }
 
@@ -722,8 +753,8 @@ __global__ void __launch_bounds__(kThreads)
   // var / std: every value is shifted by the row's first element P (shared
   // by all chunks of the row), so the Welford means stay near zero and keep
   // their digits on offset data (1e6 + N(0,1)); batches bound outliers.
-  if (MODE == M_MEAN) acc.pivot(to_f64(row[r_lo]));
-  const double P = (MODE == M_MOM) ? to_f64(row[0]) : 0.0;
+  if (mean_part<MODE>()) acc.pivot(to_f64(row[r_lo]));
+  const double P = mom_part<MODE>() ? to_f64(row[0]) : 0.0;
   // kRowsUnroll 16-B vectors in flight per lane (HBM latency cover), over
   // whole wave-wide steps only: every lane runs the same iterations, so a
   // step ends on a line boundary of a line-aligned row and no 128-B line is
@@ -739,26 +770,36 @@ __global__ void __launch_bounds__(kThreads)
     T v[kRowsUnroll][VEC];
 #pragma unroll
     for (int u = 0; u < kRowsUnroll; ++u) vload_nt<T, VEC>(row + j + u * stride, v[u]);
-    if constexpr (MODE == M_MOM) {
+    if constexpr (mom_part<MODE>()) {
       // the kRowsUnroll * VEC values in hand form one Welford batch
       double x[kRowsUnroll * VEC];
 #pragma unroll
       for (int u = 0; u < kRowsUnroll; ++u)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) x[u * VEC + k] = to_f64(v[u][k]);
+      if constexpr (MODE == M_MEANMOM) {
+        // M_MEAN's adds below, in their order, on the converted values
+        if constexpr (VEC % 2 == 0) {
+#pragma unroll
+          for (int i = 0; i < kRowsUnroll * VEC; i += 2) acc.add2(x[i], x[i + 1]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < kRowsUnroll * VEC; ++i) acc.add(x[i]);
+        }
+      }
       w.add_main<kRowsUnroll * VEC>(x, P);
       continue;
     }
 #pragma unroll
     for (int u = 0; u < kRowsUnroll; ++u) {
-      if constexpr (MODE == M_MEAN && VEC % 2 == 0) {
+      if constexpr (mean_part<MODE>() && VEC % 2 == 0) {
 #pragma unroll
         for (int k = 0; k < VEC; k += 2) acc.add2(to_f64(v[u][k]), to_f64(v[u][k + 1]));
         continue;
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        if (MODE == M_MEAN) acc.add(to_f64(v[u][k]));
+        if (mean_part<MODE>()) acc.add(to_f64(v[u][k]));
         else if (facc_mode<MODE>()) fs = fop<MODE>(fs, to_f64(v[u][k]));
         else us = bop<T, MODE>(us, belem<T, MODE>(v[u][k]));
       }
@@ -768,36 +809,37 @@ __global__ void __launch_bounds__(kThreads)
   // around one wave-wide pivot C = lane 0's Welford mean (lane 0 holds 1/64
   // of the main-loop data, so n (mean - C)^2 <= 64 M2 and S2 - S1^2/n loses
   // at most ~6 bits): plain adds, no division per lane or per butterfly step
-  const double C = (MODE == M_MOM) ? lane0_of(w.mean) : 0.0;
+  const double C = mom_part<MODE>() ? lane0_of(w.mean) : 0.0;
   double t1 = 0.0, t2 = 0.0;
   for (; j < r_hi; j += stride) {
     if (j + VEC <= r_hi) {
       T v[VEC];
       vload_nt<T, VEC>(row + j, v);
-      if constexpr (MODE == M_MOM) {
+      if constexpr (mom_part<MODE>()) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           const double y = (to_f64(v[k]) - P) - C;
           t1 += y;
           t2 = fma(y, y, t2);
         }
-        continue;
+        if constexpr (MODE == M_MOM) continue;
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        if (MODE == M_MEAN) acc.add(to_f64(v[k]));
+        if (mean_part<MODE>()) acc.add(to_f64(v[k]));
         else if (facc_mode<MODE>()) fs = fop<MODE>(fs, to_f64(v[k]));
         else us = bop<T, MODE>(us, belem<T, MODE>(v[k]));
       }
     } else {
       for (int64_t k = j; k < r_hi; ++k) {
-        if (MODE == M_MOM) {
+        if (mom_part<MODE>()) {
           const double y = (to_f64(row[k]) - P) - C;
           t1 += y;
           t2 = fma(y, y, t2);
-        } else if (MODE == M_MEAN) acc.add(to_f64(row[k]));
+        }
+        if (mean_part<MODE>()) acc.add(to_f64(row[k]));
         else if (facc_mode<MODE>()) fs = fop<MODE>(fs, to_f64(row[k]));
-        else us = bop<T, MODE>(us, belem<T, MODE>(row[k]));
+        else if (!mom_part<MODE>()) us = bop<T, MODE>(us, belem<T, MODE>(row[k]));
       }
     }
   }
@@ -806,18 +848,19 @@ __global__ void __launch_bounds__(kThreads)
   // mean: shared pivot, the S1 sums simply add; var / std: each lane's
   // Welford state as sums around C, which add.
   double m = facc_mode<MODE>() ? fs : acc.s1();
-  double wq = 0.0;
-  if constexpr (MODE == M_MOM) {
+  double ws = 0.0, wq = 0.0;  // var / std: the wave's (S1, S2) around C
+  if constexpr (mom_part<MODE>()) {
     const double dm = w.mean - C;
     const double s1 = w.n * dm;
-    m = s1 + t1;
+    ws = s1 + t1;
     wq = fma(s1, dm, w.m2) + t2;
     const auto add = [](double a, double b) { return a + b; };
-    m = wave_fold(m, lane, add);
+    ws = wave_fold(ws, lane, add);
     wq = wave_fold(wq, lane, add);
-  } else if constexpr (MODE == M_MEAN || facc_mode<MODE>()) {
+  }
+  if constexpr (mean_part<MODE>() || facc_mode<MODE>()) {
     m = wave_fold(m, lane, [](double a, double b) { return fop<MODE>(a, b); });
-  } else {
+  } else if constexpr (!mom_part<MODE>()) {
     us = wave_fold(us, lane, [](uint64_t a, uint64_t b) { return bop<T, MODE>(a, b); });
   }
   if (lane != kFoldLane) return;
@@ -826,12 +869,16 @@ __global__ void __launch_bounds__(kThreads)
   const int64_t idx = sk.final_out ? e : (c * d.O + e);
   if constexpr (MODE == M_MOM) {
     // (S1, S2) around C -> mean - P and M2
-    const double q = fma(-m, m / ntot, wq);
-    emit_mom(sk, idx, e, c, ntot, C + m / ntot, q, P);
+    const double q = fma(-ws, ws / ntot, wq);
+    emit_mom(sk, idx, e, c, ntot, C + ws / ntot, q, P);
     return;
   }
-  if (MODE == M_MEAN) m = mean_from_sums(ntot, acc.K, m);
+  if (mean_part<MODE>()) m = mean_from_sums(ntot, acc.K, m);
   emit<MODE>(sk, idx, ntot, m, 0.0, us);
+  if constexpr (MODE == M_MEANMOM) {
+    const double q = fma(-ws, ws / ntot, wq);
+    emit_kept(sk, idx, C + ws / ntot, q, P);
+  }
 }
 
 // ----------------------------------------------- exact integer var / std --
@@ -1330,7 +1377,7 @@ int launch_int_mom(const RedPlan &p, const T *s, int64_t O, int64_t R, int64_t P
 // dynamic LDS of a k_red_cols launch: the row-phase buffers when nph > 1
 template <int MODE> size_t cols_lds_bytes(int nph, int vec) {
   if (nph <= 1) return 0;
-  return (MODE == M_MOM ? (2 * (size_t)kThreads * vec + kThreads) : (size_t)kThreads * vec) * sizeof(double);
+  return (mom_part<MODE>() ? (2 * (size_t)kThreads * vec + kThreads) : (size_t)kThreads * vec) * sizeof(double);
 }
 
 template <typename T, int MODE>
@@ -1428,6 +1475,19 @@ int launch_main(int mode, int dt, const RedPlan &p, const void *src, int64_t O, 
     case M_FMIN: return launch_main_m<M_FMIN>(dt, p, src, O, R, P, I, sk, st);
     default: return launch_main_m<M_OR>(dt, p, src, O, R, P, I, sk, st);
   }
+}
+
+// bm_reduce_keep(BM_STAT_MEAN): the dual kernels, float inputs only
+int launch_keep_mean(int dt, const RedPlan &p, const void *src, int64_t O, int64_t R, int64_t P, int64_t I,
+                     Sink sk, hipStream_t st) {
+  switch (dt) {
+    case BM_F16: return launch_main_t<_Float16, M_MEANMOM>(p, src, O, R, P, I, sk, st);
+    case BM_F32: return launch_main_t<float, M_MEANMOM>(p, src, O, R, P, I, sk, st);
+    case BM_F64: return launch_main_t<double, M_MEANMOM>(p, src, O, R, P, I, sk, st);
+    default: break;
+  }
+  bm_set_error("bm_reduce_keep: dtype %d is not a float dtype", dt);
+  return BM_E_ARG;
 }
 
 // block-per-output combine for few outputs from many parts
@@ -1648,6 +1708,54 @@ extern "C" int bm_reduce_moments(const void *src, int in_dtype, int64_t O, int64
   sk.os = out_std;
   return run_reduce(BM_STAT_VAR, src, in_dtype, O, R, I, sk, workspace, workspace_bytes,
                     (hipStream_t)stream, who, row_pitch);
+}
+
+// bm_reduce / bm_reduce_rows of a mean, var or std whose one read also leaves
+// the BM_STAT_VAR state behind.  var / std: the M_MOM kernels store the state
+// they finalise; mean: the M_MEANMOM kernels run both accumulations.  Integer
+// inputs and chunked plans (partials in a workspace, merged by the combine
+// kernel) run the plain launches: *kept = 0.
+extern "C" int bm_reduce_keep(int stat, const void *src, int in_dtype, int64_t O, int64_t R, int64_t I,
+                              int64_t row_pitch, void *out, int out_dtype, void *state, int *kept,
+                              void *workspace, size_t workspace_bytes, void *stream) {
+  const char *who = "bm_reduce_keep";
+  int rc = check_args(stat, in_dtype, O, R, I, who);
+  if (rc) return rc;
+  if (stat != BM_STAT_MEAN && stat != BM_STAT_VAR && stat != BM_STAT_STD) {
+    bm_set_error("%s: stat %d is not mean, var or std", who, stat);
+    return BM_E_ARG;
+  }
+  if (!src || !out || !state || !kept) { bm_set_error("%s: null pointer", who); return BM_E_ARG; }
+  if (!is_float(out_dtype)) {
+    bm_set_error("%s: out_dtype %d is not a float dtype", who, out_dtype);
+    return BM_E_ARG;
+  }
+  if (row_pitch < R || (I > 1 && row_pitch != R)) {
+    bm_set_error("%s: row_pitch %lld does not fit R=%lld, I=%lld (>= R, and R itself unless I == 1)", who,
+                 (long long)row_pitch, (long long)R, (long long)I);
+    return BM_E_ARG;
+  }
+  *kept = 0;
+  Sink sk{};
+  sk.out = out;
+  sk.out_dtype = out_dtype;
+  sk.stat = stat;
+  sk.final_out = 1;
+  const RedPlan p = plan_reduce(in_dtype, O, R, I, src, row_pitch);
+  if (!is_float(in_dtype) || p.nchunks > 1)
+    return run_reduce(stat, src, in_dtype, O, R, I, sk, workspace, workspace_bytes, (hipStream_t)stream, who,
+                      row_pitch);
+  sk.k0 = (double *)state;
+  sk.k1 = (double *)state + O * I;
+  if (stat == BM_STAT_MEAN) {
+    rc = launch_keep_mean(in_dtype, p, src, O, R, row_pitch, I, sk, (hipStream_t)stream);
+    if (!rc) rc = check_launch(who);
+  } else {
+    rc = run_reduce(stat, src, in_dtype, O, R, I, sk, workspace, workspace_bytes, (hipStream_t)stream, who,
+                    row_pitch);
+  }
+  if (!rc) *kept = 1;
+  return rc;
 }
 
 extern "C" int bm_reduce_state_bytes(int stat, int in_dtype, int64_t nout, size_t *bytes) {

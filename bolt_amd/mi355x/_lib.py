@@ -51,6 +51,9 @@ SIGNATURES = {
     "bm_reduce_moments": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                      _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p,
                                      _c.c_size_t, _c.c_void_p]),
+    "bm_reduce_keep": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                  _c.c_void_p, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p,
+                                  _c.c_size_t, _c.c_void_p]),
     "bm_reduce_combine_moments": (_c.c_int, [_c.c_int, _c.c_void_p, _i64p, _c.c_int, _c.c_int64,
                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "bm_reduce_state_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_size_t)]),

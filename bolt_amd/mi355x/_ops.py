@@ -305,15 +305,35 @@ class HipBackend(object):
             return None, 0
         return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
-    def reduce(self, stat, src, code, O, R, I, out, out_code):
+    # reduce / reduce_rows take ``state=`` (see _keep): array.py asks for it
+    # only of a backend with this attribute
+    keeps_moments = True
+
+    def _keep(self, stat, src, code, O, R, I, pitch, out, out_code, state):
+        """bm_reduce_keep: the mean / var / std launch that also stores the
+        STAT_VAR state of its one read into ``state`` -> True if it did."""
+        ws, nws = self._workspace(stat, code, O, R, I, src.device)
+        kept = ctypes.c_int(0)
+        rc = self.lib.bm_reduce_keep(stat, src.data_ptr(), code, O, R, I, pitch, out.data_ptr(), out_code,
+                                     state.data_ptr(), ctypes.byref(kept),
+                                     ws.data_ptr() if ws is not None else None, nws, raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_reduce_keep")
+        return bool(kept.value)
+
+    def reduce(self, stat, src, code, O, R, I, out, out_code, state=None):
+        if state is not None:
+            return self._keep(stat, src, code, O, R, I, R, out, out_code, state)
         ws, nws = self._workspace(stat, code, O, R, I, src.device)
         rc = self.lib.bm_reduce(stat, src.data_ptr(), code, O, R, I, out.data_ptr(), out_code,
                                 ws.data_ptr() if ws is not None else None, nws, raw_stream(src.device))
         if rc:
             _lib.check(rc, "bm_reduce")
 
-    def reduce_rows(self, stat, src, code, O, R, pitch, out, out_code):
+    def reduce_rows(self, stat, src, code, O, R, pitch, out, out_code, state=None):
         """reduce over O rows of R elements that start ``pitch`` elements apart."""
+        if state is not None:
+            return self._keep(stat, src, code, O, R, 1, pitch, out, out_code, state)
         ws, nws = self._workspace(stat, code, O, R, 1, src.device)
         rc = self.lib.bm_reduce_rows(stat, src.data_ptr(), code, O, R, pitch, out.data_ptr(), out_code,
                                      ws.data_ptr() if ws is not None else None, nws, raw_stream(src.device))

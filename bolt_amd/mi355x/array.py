@@ -208,6 +208,30 @@ def _aligned_vshape_of(shape, split, axis):
     return None if vs == kept else vs
 
 
+# mean() / var() / std() over the same axes of one array: the first call's read
+# also stores the StatCounter state (n, mean, M2 -- statcounter.py:30-48, which
+# the reference's _stat builds whole on every call) and a later var() / std()
+# is finished from it (bm_reduce_combine of one part) without reading the
+# array.  Records never change after construction, so the state is an
+# invariant of (array, axes).  Kept only when the second read would come from
+# HBM -- more bytes than the 256 MiB Infinity Cache -- and when the state (16 B
+# per output) is at most 1/64 of the bytes read: its store and the memory it
+# holds stay under 1.6% of the read.  One GPU, float inputs, row reductions
+# (I == 1) whose plan does not split R into chunks (bm_reduce_keep).  A later mean() reads again: its bits
+# come from other arithmetic than the state's mean.  unpersist() releases the
+# states; KEEP_MOMENTS = False (BOLT_AMD_KEEP_MOMENTS=0) keeps none.
+KEEP_MOMENTS = os.environ.get("BOLT_AMD_KEEP_MOMENTS", "1") != "0"
+_KEEP_MIN_BYTES = 256 << 20
+_KEEP_STATE_DIV = 64
+# Column reductions (I > 1) keep nothing: storing the state cost their launch
+# +3.1% on one box and +11% on another on the 64 GiB target's shape at 1/8 of
+# its rows (1.280 / 1.383 against 1.236-1.243 ms, spread 0.015 ms), the same for
+# the dual mean launch and for the var / std launch that only adds the stores,
+# where the rows kernel's is within its spread (C2: +0.003 ms of 0.303;
+# profiles/moments_kept_ab.log).  True: tools/moments_kept_ab.py --keep-cols,
+# the run that measured it, and the tests of the column branches.
+_KEEP_COLS = False
+
 _REDUCE_PLANS = {}  # (local shape, axes, stat, dtype, world) -> device reduction plan
 _MOMENT_PLANS = {}  # (local shape, axes, dtype, shape, world) -> device plan of stats() (one read, several moments)
 
@@ -503,8 +527,10 @@ class BoltArrayMI355X(BoltArray):
         self._cached = True
 
     def unpersist(self):
-        """(array.py:43-47) -- the records stay in HBM; clears the flag."""
+        """(array.py:43-47) -- the records stay in HBM; clears the flag and
+        releases the moment states kept by mean / var / std (see KEEP_MOMENTS)."""
         self._cached = False
+        self.__dict__.pop("_kept", None)
 
     # ------------------------------------------------------------ movement
     def _permute(self, perm, split):
@@ -1124,6 +1150,9 @@ class BoltArrayMI355X(BoltArray):
                 _REDUCE_PLANS.clear()
             _REDUCE_PLANS[pkey] = plan
         axset, kept, out_shape, out_dtype, code, ocode, perm, O, R, I, nloc, loc_out, nout = plan
+        held = self.__dict__.get("_kept")
+        if held and KEEP_MOMENTS and stat in (_lib.STAT_VAR, _lib.STAT_STD) and tuple(axset) in held:
+            return self._from_kept(held[tuple(axset)], stat, code, ocode, out_dtype, out_shape), out_dtype
         pbuf = self.__dict__.get("_pbuf")
         if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and ctx.world_size > 1 \
                 and 0 not in axset:
@@ -1139,12 +1168,13 @@ class BoltArrayMI355X(BoltArray):
         if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and nloc and ctx.world_size == 1:
             # last-axis statistic of a row-padded array: read the rows in place
             be = backend_for(pbuf.device)
+            st = self._keep_state(be, pbuf.device, axset, stat, code, nout, nloc, False)
             host = host_result(be, nout * out_dtype.itemsize, pbuf.device)
             if host is not None:
-                be.reduce_rows(stat, pbuf, code, O, R, self._pitch, host, ocode)
+                self._keeping(axset, be.reduce_rows, (stat, pbuf, code, O, R, self._pitch, host, ocode), st, R, nout)
                 return finish_host_result(host, pbuf.device, out_dtype, out_shape), out_dtype
             out = _empty(nout * out_dtype.itemsize, pbuf.device)
-            be.reduce_rows(stat, pbuf, code, O, R, self._pitch, out, ocode)
+            self._keeping(axset, be.reduce_rows, (stat, pbuf, code, O, R, self._pitch, out, ocode), st, R, nout)
             return to_host(out, out_dtype, out_shape), out_dtype
         if pbuf is not None and perm is None and I > 1 and I % lshape[-1] == 0 and nloc and ctx.world_size == 1:
             # leading / middle axes of a row-padded array: the columns run over
@@ -1155,13 +1185,16 @@ class BoltArrayMI355X(BoltArray):
             Rl, P = lshape[-1], self._pitch
             Ip = I // Rl * P
             nb = O * Ip * out_dtype.itemsize
+            # the kept state holds the pad columns' states too: dropped as here
+            st = self._keep_state(be, pbuf.device, axset, stat, code, O * Ip, O * R * Ip, True)
+            drop = (O, I // Rl, P, Rl)
             host = host_result(be, nb, pbuf.device)
             if host is not None:
-                be.reduce(stat, pbuf, code, O, R, Ip, host, ocode)
+                self._keeping(axset, be.reduce, (stat, pbuf, code, O, R, Ip, host, ocode), st, R, O * Ip, drop)
                 full = finish_host_result(host, pbuf.device, out_dtype, (O, I // Rl, P))
             else:
                 out = _empty(nb, pbuf.device)
-                be.reduce(stat, pbuf, code, O, R, Ip, out, ocode)
+                self._keeping(axset, be.reduce, (stat, pbuf, code, O, R, Ip, out, ocode), st, R, O * Ip, drop)
                 full = to_host(out, out_dtype, (O, I // Rl, P))
             return np.ascontiguousarray(full[:, :, :Rl]).reshape(out_shape), out_dtype
         if pbuf is not None and perm is None and O == 1 and I == 1 and R == nloc and nloc \
@@ -1188,13 +1221,15 @@ class BoltArrayMI355X(BoltArray):
         if ctx.world_size == 1 or 0 not in axset:
             # every output lives on this rank (or this rank's slab of them)
             host = host_result(be, nout * out_dtype.itemsize, dev) if ctx.world_size == 1 and nloc else None
+            # (a state kept after the permute above serves later calls without it)
+            st = self._keep_state(be, dev, axset, stat, code, nout, nloc, I > 1) if nout and nloc else None
             if host is not None:
                 # the kernel stores the result into page-locked host memory
-                be.reduce(stat, src, code, O, R, I, host, ocode)
+                self._keeping(axset, be.reduce, (stat, src, code, O, R, I, host, ocode), st, R, nout)
                 return finish_host_result(host, dev, out_dtype, out_shape), out_dtype
             out = _empty(nout * out_dtype.itemsize, dev)
             if nout and nloc:
-                be.reduce(stat, src, code, O, R, I, out, ocode)
+                self._keeping(axset, be.reduce, (stat, src, code, O, R, I, out, ocode), st, R, nout)
             if ctx.world_size > 1:
                 sizes = []
                 for lo, hi in ctx.bounds(self._shape[0]):
@@ -1225,6 +1260,52 @@ class BoltArrayMI355X(BoltArray):
         out = _empty(nout * out_dtype.itemsize, dev)
         be.reduce_combine(stat, code, states, counts, nout, out, ocode)
         return to_host(out, out_dtype, out_shape), out_dtype
+
+    def _keep_state(self, be, dev, axset, stat, code, nlaunch, nread, cols):
+        """The buffer a mean / var / std launch of ``nlaunch`` outputs over
+        ``nread`` elements stores its STAT_VAR state into, or None where none
+        is kept (the rule is at KEEP_MOMENTS) or these axes' is held already.
+        ``cols``: the launch is a column reduction (I > 1)."""
+        if not KEEP_MOMENTS or stat not in _MOMENTS or self._dtype.kind != 'f' or self._ctx.world_size != 1 \
+                or not getattr(be, "keeps_moments", False):
+            return None
+        if cols and not _KEEP_COLS:
+            return None
+        held = self.__dict__.get("_kept")
+        if held and tuple(axset) in held:
+            return None
+        nbytes = nread * self._dtype.itemsize
+        if nbytes <= _KEEP_MIN_BYTES or 16 * nlaunch > nbytes // _KEEP_STATE_DIV:
+            return None
+        return _empty(be.state_bytes(_lib.STAT_VAR, code, nlaunch), dev)
+
+    def _keeping(self, axset, launch, args, state, count, nlaunch, drop=None):
+        """The branch's one reduce / reduce_rows call; with ``state`` the
+        launch may keep its STAT_VAR state there, remembered for these axes."""
+        if state is None:
+            launch(*args)
+        elif launch(*args, state=state):
+            self.__dict__.setdefault("_kept", {})[tuple(axset)] = (state, count, nlaunch, drop)
+
+    def _from_kept(self, entry, stat, code, ocode, out_dtype, out_shape):
+        """var / std finished from a kept state: one reduce_combine of one part
+        into the host result of the branch that kept it, no read of the array."""
+        state, count, nlaunch, drop = entry
+        dev = state.device
+        be = backend_for(dev)
+        shape = out_shape if drop is None else drop[:3]
+        host = host_result(be, nlaunch * out_dtype.itemsize, dev)
+        with np.errstate(all="ignore"):  # pad columns' unwritten values, as in _combine_moments
+            if host is not None:
+                be.reduce_combine(stat, code, state, [count], nlaunch, host, ocode)
+                full = finish_host_result(host, dev, out_dtype, shape)
+            else:
+                out = _empty(nlaunch * out_dtype.itemsize, dev)
+                be.reduce_combine(stat, code, state, [count], nlaunch, out, ocode)
+                full = to_host(out, out_dtype, shape)
+        if drop is None:
+            return full
+        return np.ascontiguousarray(full[:, :, :drop[3]]).reshape(out_shape)
 
     def _padded_all_moments(self, pbuf, stat, code, out_dtype, out_shape):
         """mean / var / std over every axis of a row-padded float array, read in

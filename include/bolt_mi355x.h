@@ -285,6 +285,28 @@ int bm_reduce_moments(const void *src, int in_dtype, int64_t O, int64_t R,
                       size_t workspace_bytes, void *stream);
 
 /*
+ * bm_reduce_keep -- bm_reduce / bm_reduce_rows of a mean, variance or standard
+ * deviation that keeps what its read saw: the reference's _stat
+ * (bolt/spark/array.py:284-334) builds the whole StatCounter (n, mu, m2:
+ * bolt/spark/statcounter.py:30-48) on every call and reads one moment of it;
+ * an array's records never change, so the counter of (array, axes) is kept
+ * and a later var / std is bm_reduce_combine of it (one part, count R) with
+ * no read of the array.  stat is BM_STAT_MEAN, BM_STAT_VAR or BM_STAT_STD;
+ * the layout, row_pitch, out and out_dtype (a float dtype) are
+ * bm_reduce_moments'; the workspace is bm_reduce_workspace_bytes of stat.
+ * out receives exactly the bytes bm_reduce / bm_reduce_rows writes.  state
+ * (bm_reduce_state_bytes(BM_STAT_VAR, in_dtype, O*I) bytes, device memory)
+ * receives from the same read the two planes bm_reduce_state(BM_STAT_VAR)
+ * stores, bit for bit -- absolute mean[O*I], then M2[O*I] -- and *kept = 1.
+ * Integer inputs and plans that split R into chunks run the plain launches:
+ * state is left untouched and *kept = 0.
+ */
+int bm_reduce_keep(int stat, const void *src, int in_dtype, int64_t O, int64_t R,
+                   int64_t I, int64_t row_pitch, void *out, int out_dtype,
+                   void *state, int *kept, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
+/*
  * Partial reduction state for the multi-GPU merge (the per-partition
  * StatCounter of array.py:321-322).  `state` receives, for O*I outputs:
  *   MEAN/VAR/STD: two float64 planes, mean[O*I] then M2[O*I] (count = R);
