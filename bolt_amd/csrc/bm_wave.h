@@ -1,0 +1,74 @@
+// bm_wave.h -- wave-level helpers shared by the row kernels of bm_reduce.hip
+// and bm_standardize.hip (gfx950 only): the float64 element conversion, the
+// deterministic DPP fold of the 64 lanes and the XCD-aware block order.
+#pragma once
+
+#include "bm_common.h"
+
+template <typename T> __device__ __forceinline__ double to_f64(T x) { return (double)x; }
+template <> __device__ __forceinline__ double to_f64<_Float16>(_Float16 x) { return (double)(float)x; }
+
+// ---- wave fold through DPP ----
+// A 64-bit lane value moved by a DPP modifier of v_mov (two 32-bit halves, the
+// same source lane): the cross-lane read stays in the VALU, no LDS round trip
+// as __shfl_xor's ds_bpermute takes.  Controls (GFX9 DPP): quad_perm [1,0,3,2]
+// = 0xB1 (lane ^ 1), [2,3,0,1] = 0x4E (lane ^ 2), row_half_mirror 0x141
+// (lane 7-i of its 8), row_mirror 0x140 (lane 15-i of its row), row_bcast15
+// 0x142 (lane 15 of row r -> row r+1), row_bcast31 0x143 (lane 31 -> rows 2, 3).
+template <int CTRL, typename V> __device__ __forceinline__ V dpp_mov(V v) {
+  static_assert(sizeof(V) == 8, "64-bit lane values");
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(V, ((uint64_t)hi << 32) | lo);
+}
+// Lane 63 receives op over all 64 lanes, combined in lane order: every step
+// combines (lower lanes, upper lanes), so the result equals a left fold over
+// lanes 0..63 for any associative op (first NaN / first of equal values wins,
+// as in a sequential scan).  Steps 1-4 leave identical bits in the lanes that
+// feed the next step (both lanes of a pair form op(lower, upper)); steps 5-6
+// fold the four 16-lane rows.  Requires all 64 lanes active.
+template <typename V, typename F> __device__ __forceinline__ V wave_fold(V v, int lane, F op) {
+  V p = dpp_mov<0xB1>(v);
+  v = (lane & 1) ? op(p, v) : op(v, p);
+  p = dpp_mov<0x4E>(v);
+  v = (lane & 2) ? op(p, v) : op(v, p);
+  p = dpp_mov<0x141>(v);
+  v = (lane & 4) ? op(p, v) : op(v, p);
+  p = dpp_mov<0x140>(v);
+  v = (lane & 8) ? op(p, v) : op(v, p);
+  p = dpp_mov<0x142>(v);
+  if (lane & 16) v = op(p, v);  // lane 31 = rows 0+1, lane 63 = rows 2+3
+  p = dpp_mov<0x143>(v);
+  if (lane & 32) v = op(p, v);  // lane 63 = (rows 0+1) + (rows 2+3)
+  return v;
+}
+constexpr int kFoldLane = 63;
+// lane L's value in every lane (v_readlane into a scalar register)
+template <int L> __device__ __forceinline__ double lane_of(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, L);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), L);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane0_of(double v) { return lane_of<0>(v); }
+
+// ---- block order of the row kernels ----
+// Round-robin dispatch puts block b on XCD b % 8: give XCD x the x-th
+// contiguous eighth of the rows, so the 128-B lines two neighbouring rows
+// share are fetched into one L2 instead of two (runs of 16 / 128 / 1024
+// blocks per XCD in turn: no better, padded rows 5% worse at 16,
+// profiles/r05w_xcd_runs.txt).  XCD x starts its eighth x * SKEW blocks in
+// and wraps, so the eight XCDs are never a power-of-two distance apart: on
+// C2's padded rows (8192-B pitch, eighths 256 MiB apart) mean / std
+// -1.2% / -1.0% over 3 alternating rounds (profiles/r05zd_xcd_skew.txt)
+constexpr uint64_t kRedXcdSkew = 37;
+__device__ __forceinline__ uint64_t rows_block() {
+  uint64_t bid = blockIdx.x;
+  const uint64_t g8 = gridDim.x / 8 * 8;
+  if (bid < g8) {
+    const uint64_t E = g8 / 8;
+    bid = (bid % 8) * E + (bid / 8 + (bid % 8) * kRedXcdSkew) % E;
+  }
+  return bid;
+}

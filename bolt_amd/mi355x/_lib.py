@@ -56,6 +56,10 @@ SIGNATURES = {
                                   _c.c_size_t, _c.c_void_p]),
     "bm_reduce_combine_moments": (_c.c_int, [_c.c_int, _c.c_void_p, _i64p, _c.c_int, _c.c_int64,
                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "bm_standardize_rows": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
+                                       _c.c_int, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int), _c.c_void_p]),
+    "bm_standardize_apply": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p]),
     "bm_reduce_state_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_size_t)]),
     "bm_reduce_state": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64,
                                    _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),

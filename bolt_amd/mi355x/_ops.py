@@ -351,6 +351,29 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_reduce_moments")
 
+    def standardize_rows(self, src, code, O, R, src_pitch, dst, out_code, dst_pitch, scale):
+        """dst rows = (src rows - their mean) [/ their std if ``scale``], O rows
+        of R elements, pitches in elements: one read and one write
+        (bm_standardize_rows) -> True if the rows were taken, False (nothing
+        launched) when they do not fit the kernels."""
+        taken = ctypes.c_int(0)
+        rc = self.lib.bm_standardize_rows(src.data_ptr(), code, O, R, src_pitch, dst.data_ptr(), out_code,
+                                          dst_pitch, 1 if scale else 0, ctypes.byref(taken),
+                                          raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_standardize_rows")
+        return bool(taken.value)
+
+    def standardize_apply(self, src, code, O, R, I, src_pitch, mean, std, dst, out_code, dst_pitch):
+        """dst[o,r,i] = (src[o,r,i] - mean[o*I+i]) [/ std[o*I+i]] with float64
+        device planes ``mean`` / ``std`` (None: centre only); rows ``src_pitch``
+        / ``dst_pitch`` elements apart when I == 1 (bm_standardize_apply)."""
+        rc = self.lib.bm_standardize_apply(src.data_ptr(), code, O, R, I, src_pitch, mean.data_ptr(),
+                                           std.data_ptr() if std is not None else None, dst.data_ptr(),
+                                           out_code, dst_pitch, raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_standardize_apply")
+
     def state_bytes(self, stat, code, nout):
         n = ctypes.c_size_t(0)
         _lib.check(self.lib.bm_reduce_state_bytes(stat, code, nout, ctypes.byref(n)), "bm_reduce_state_bytes")

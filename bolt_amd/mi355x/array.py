@@ -17,6 +17,10 @@ Operations and what replaces the Spark machinery:
   stats: several of mean / var / std from ONE read (the StatCounter's
       stats='all', statcounter.py:30-48): the variance's launch sequence
       storing every moment asked for (bm_reduce_moments).
+  center / zscore: every record minus its mean [over its standard
+      deviation] along an axis, a device array of the same shape: rows over
+      the last axis in one read and one write (bm_standardize_rows), other
+      axes as one moments read plus bm_standardize_apply.
   toarray / tolocal: D2H (+ all_gather of the slabs).
 """
 import collections
@@ -1511,6 +1515,151 @@ class BoltArrayMI355X(BoltArray):
                     arr = np.expand_dims(arr, axis=i)
             out[f] = BoltArrayLocal(arr).toscalar()
         return Stats(count=count, **out)
+
+    def _standardized(self, axis, scale):
+        """center (``scale`` False) / zscore (True) over ``axis``: a new device
+        array of this array's shape and split, every record minus its mean [over
+        its population standard deviation], in the dtype of ``record - 0.0``.
+
+        Planned with plan.reduce_layout like _reduced_moments, and what it costs:
+          * the last axis (rows dense or row-padded, read in place): one
+            bm_standardize_rows launch, one read and one write; a padded input
+            whose item size is kept gives a result padded alike;
+          * rows that launch does not take, and reduced axes that form one
+            block: the float64 mean / std planes from one read
+            (bm_reduce_moments), then bm_standardize_apply: two reads and one
+            write;
+          * reduced axes that are not one block: permuted to the front first
+            and the result permuted back -- two more reads and writes;
+          * a row-padded input over other axes than the last: copied to a dense
+            temporary first (the array itself stays padded) -- one more read
+            and write;
+          * the sharded axis reduced: per-rank states, gathered and merged in
+            rank order as in _reduced_moments, then applied to this rank's slab.
+        Moment states (KEEP_MOMENTS) are neither used nor left."""
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        ctx = self._ctx
+        lshape = self._local_shape
+        out_dtype = stat_dtype(self._dtype, (1,))
+        code, ocode = dtype_code(self._dtype), dtype_code(out_dtype)
+        dev = self._device
+        if self.size == 0:
+            return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+        be = backend_for(dev)
+        axset = sorted(set(int(a) for a in ax))
+        perm, O, R, I = reduce_layout(lshape, axset)
+        nloc = int(np.prod(lshape, dtype=np.int64))
+        es, oes = self._dtype.itemsize, out_dtype.itemsize
+        d = self.__dict__
+        pbuf, P = d.get("_pbuf"), d.get("_pitch")
+        # every reduced record lies whole on this rank
+        local = ctx.world_size == 1 or 0 not in axset
+        # the reduced axis is the last one: rows, a pitch apart
+        rows_last = perm is None and I == 1 and local and (pbuf is None or R == lshape[-1])
+
+        if rows_last and nloc and hasattr(be, "standardize_rows"):
+            keep_pad = pbuf is not None and oes == es
+            dp = P if keep_pad else R
+            dst = _empty(O * dp * oes, dev)
+            src, sp = (pbuf, P) if pbuf is not None else (self._data, R)
+            if be.standardize_rows(src, code, O, R, sp, dst, ocode, dp, scale):
+                if not keep_pad:
+                    return self._like(dst, self._shape, self._split, dtype=out_dtype)
+                new = self._derive_padded(dst, P, self._shape, self._split)
+                new.__dict__["_dtype"] = out_dtype
+                return new
+
+        pitch = R
+        if perm is not None:
+            # the reduced axes first (_align's swap): a padded array is read in place
+            src = _empty(nloc * es, dev)
+            pshape = [lshape[p] for p in perm]
+            if pbuf is not None and nloc:
+                pstr = _padded_strides(lshape, P)
+                be.copy_strided(pbuf, 0, src, 0, pshape, [pstr[p] for p in perm],
+                                _padded_strides(pshape, pshape[-1]), es)
+            elif nloc:
+                be.permute(self._data, lshape, perm, es, src)
+        elif pbuf is not None and rows_last:
+            src, pitch = pbuf, P
+        elif pbuf is not None:
+            src = _empty(nloc * es, dev)
+            if nloc:
+                be.copy_strided(pbuf, 0, src, 0, [nloc // lshape[-1], lshape[-1]], [P, 1], [lshape[-1], 1], es)
+        else:
+            src = self._data
+
+        want = ('mean', 'std') if scale else ('mean',)
+        f64 = np.dtype(np.float64)
+        fcode = dtype_code(f64)
+        planes = None
+        if local:
+            nplane = O * I
+            if nloc:
+                _, planes = _launch_moments(be, src, es, code, fcode, f64, want, O, R, I, pitch, False)
+        else:
+            # the sharded axis is reduced: one STAT_VAR state per rank, gathered
+            # and merged in rank order; every rank takes part, its launches only
+            # where its slab has elements
+            nplane = int(np.prod([self._shape[i] for i in range(self.ndim) if i not in axset], dtype=np.int64))
+            if ctx.world_size > _lib.MAX_COMBINE_PARTS:
+                raise NotImplementedError("reductions over the sharded axis merge at most %d ranks (got %d)"
+                                          % (_lib.MAX_COMBINE_PARTS, ctx.world_size))
+            sbytes = be.state_bytes(_lib.STAT_VAR, code, nplane)
+            state = _empty(sbytes, dev)
+            if nloc:
+                be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
+            else:
+                state.zero_()
+            counts = [(hi - lo) * int(np.prod([self._shape[i] for i in axset if i != 0], dtype=np.int64))
+                      for lo, hi in ctx.bounds(self._shape[0])]
+            states = all_gather_bytes(ctx, state, [sbytes] * ctx.world_size)
+            _, planes = _combine_moments(be, code, fcode, f64, want, states, counts, nplane, False)
+
+        dst = _empty(nloc * oes, dev)
+        if nloc:
+            mean = planes[:nplane * 8]
+            std = planes[nplane * 8:2 * nplane * 8] if scale else None
+            if hasattr(be, "standardize_apply"):
+                be.standardize_apply(src, code, O, R, I, pitch, mean, std, dst, ocode, R)
+            else:
+                # an executor without the entry points (the CPU test executor):
+                # torch float64 arithmetic on views of the bytes, padded rows
+                # through a strided view
+                import torch
+                from bolt_amd.mi355x import functional as F
+                if pitch != R:
+                    x = F.view(src[:O * pitch * es], (O, pitch), self._dtype)[:, :R].unsqueeze(2)
+                else:
+                    x = F.view(src, (O, R, I), self._dtype)
+                y = x.to(torch.float64) - F.view(mean, (O, 1, I), f64)
+                if scale:
+                    y = y / F.view(std, (O, 1, I), f64)
+                dst = F.as_bytes(y.to(F.torch_dtype(out_dtype)).contiguous())
+            if perm is not None:
+                back = _empty(nloc * oes, dev)
+                be.permute(dst, pshape, [int(i) for i in np.argsort(perm)], oes, back)
+                dst = back
+        return self._like(dst, self._shape, self._split, dtype=out_dtype)
+
+    def center(self, axis=None):
+        """Every record minus its mean over ``axis`` (None: every axis), as a
+        new array of the same shape, split and sharding, resident on the
+        device; its dtype is that of ``record - 0.0`` (float16 / float32 keep
+        theirs, every other dtype gives float64).  ``axis`` is taken as mean()
+        takes it.  The mean is formed, and subtracted, in float64, and the
+        result rounded once.  An addition to the reference's API (the
+        reference subtracts the array mean() returns, on the host)."""
+        return self._standardized(axis, False)
+
+    def zscore(self, axis=None):
+        """center(axis) divided by the population standard deviation (ddof = 0,
+        the StatCounter's stdev, statcounter.py:109-130) over ``axis``; the
+        division is float64's, before the one rounding.  A record of zero
+        variance gives nan (0/0, as numpy), a record holding a nan gives nan
+        throughout.  An addition to the reference's API."""
+        return self._standardized(axis, True)
 
     def _stat(self, axis=None, func=None, name=None, keepdims=False):
         """Statistic over ``axis`` (array.py:284-334); results are host arrays / scalars."""

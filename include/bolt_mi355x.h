@@ -307,6 +307,50 @@ int bm_reduce_keep(int stat, const void *src, int in_dtype, int64_t O, int64_t R
                    size_t workspace_bytes, void *stream);
 
 /*
+ * bm_standardize_rows -- center / z-score of rows in one read and one write:
+ *   dst[o*dst_pitch + r] = (src[o*src_pitch + r] - mean_o) [/ std_o],  r < R,
+ * mean_o and std_o (population, ddof = 0: bolt/spark/statcounter.py:109-130)
+ * over row o's R elements; scale = 0 subtracts the mean only, scale = 1 also
+ * divides.  No reference call site: the reference has no center / zscore (an
+ * API addition, like bm_reduce_moments' stats()); the pipelines built on it
+ * subtract and divide on the host from what mean() / std() return
+ * (bolt/spark/array.py:336-379).  Pitches are in elements, >= R; the pad is
+ * neither read nor written.  out_dtype must be the statistics dtype of
+ * in_dtype (float16 / float32 keep theirs, every other dtype gives float64).
+ * Each row is held in registers between its read and its write -- one wave per
+ * row, or one 256-thread block per longer row; the moments are float64
+ * two-pass sums over the held values, the subtraction and the (true) division
+ * are float64, rounded once to out_dtype; the same input gives the same bytes.
+ * A row of zero variance centres to zeros and scales to nan (0/0); a nan makes
+ * its whole row nan.  *taken = 1 when the rows were written; *taken = 0 and
+ * nothing launched when a row is longer than the kernels hold on chip, or
+ * when longer rows are too few to give each a block (bm_reduce_moments, then
+ * bm_standardize_apply, serve those).  O == 0 or R == 0 writes nothing
+ * (*taken = 1).  Arguments are checked before any launch.
+ */
+int bm_standardize_rows(const void *src, int in_dtype, int64_t O, int64_t R,
+                        int64_t src_pitch, void *dst, int out_dtype,
+                        int64_t dst_pitch, int scale, int *taken, void *stream);
+
+/*
+ * bm_standardize_apply -- the elementwise half of center / z-score for every
+ * layout bm_standardize_rows does not take: over bm_reduce's [O][R][I],
+ *   dst[o,r,i] = (src[o,r,i] - mean[o*I+i]) [/ std[o*I+i]],
+ * mean / std being float64 device planes of O*I values (bm_reduce_moments or
+ * bm_reduce_combine_moments with out_dtype BM_F64); std NULL: centre only.
+ * No reference call site (an API addition, see bm_standardize_rows).  With
+ * I == 1 the rows of src / dst are src_pitch / dst_pitch elements apart
+ * (>= R); with I > 1 both pitches must be R.  out_dtype and the arithmetic
+ * are bm_standardize_rows'.  The planes are read through the cache, the array
+ * with streaming loads and stores: one read and one write of the array.
+ * Any of O, R, I == 0 writes nothing.  Arguments are checked before any launch.
+ */
+int bm_standardize_apply(const void *src, int in_dtype, int64_t O, int64_t R,
+                         int64_t I, int64_t src_pitch, const double *mean,
+                         const double *std, void *dst, int out_dtype,
+                         int64_t dst_pitch, void *stream);
+
+/*
  * Partial reduction state for the multi-GPU merge (the per-partition
  * StatCounter of array.py:321-322).  `state` receives, for O*I outputs:
  *   MEAN/VAR/STD: two float64 planes, mean[O*I] then M2[O*I] (count = R);
