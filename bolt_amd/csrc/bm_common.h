@@ -169,3 +169,10 @@ __device__ __forceinline__ void vstore_nt(T *p, const T (&in)[N]) {
 
 // thread-local error channel (bm_last_error)
 void bm_set_error(const char *fmt, ...);
+
+// bm_reduce.hip, for bm_copy_strided_moments: Chan merge, in part order, of
+// the per-b-tile states a moments transpose left (part p: K[nrows], (mean -
+// K)[nrows], M2[nrows] over min(tb, R - p * tb) values) into the two-plane BM_STAT_VAR
+// state of bm_reduce_state (mean[nrows], M2[nrows]).
+int bm_merge_tile_moments(const double *parts, int64_t nparts, int64_t tb, int64_t R, int64_t nrows,
+                          double *state, hipStream_t stream);

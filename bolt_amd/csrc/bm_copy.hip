@@ -21,10 +21,12 @@
 //
 // All are HBM-bound; algorithmic bytes = 2 * N * elem_bytes.
 #include "bm_common.h"
+#include "bm_wave.h"
 #include "../../include/bolt_mi355x.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -173,9 +175,56 @@ __device__ __forceinline__ int64_t arow(const TransDesc &d, int64_t a) {
   return (a - hi * (int64_t)d.La1.d) * d.da + hi * d.da2;
 }
 
-template <typename T, int TA, int TB, int VA, int VB, bool FUSED = false>
+
+// Moments of the tile rows (bm_copy_strided_moments).  F = float / double, the
+// real type of the T words: besides moving the tile, the store side leaves
+// the state of the min(TB, Lb - b0) values of every tile row, part-major:
+// part = b-tile, three float64 planes of nrows each: K, mean - K and M2.  (The
+// mean stays split: K + (mean - K) rounded to one double loses the digits of
+// offset data, 1e6 + N(0,1), that the merge's delta between two tiles needs.)
+// The store side, not the load side, does the arithmetic: there the lanes of
+// one wave hold a whole tile row (f32 64x256: all 64 lanes, 4 values each),
+// so a row costs DPP adds (bm_wave.h's dpp_mov) and 72 B of LDS; on the load
+// side a lane owns columns and the kThreads / NVA row groups would merge through 16 KiB of (mean, M2) staging next to the 66.5-KiB tile,
+// more than two blocks per CU leave room for.  Sums of (x - K), (x - K)^2 in
+// float64 around K = the row's first value in the tile (one of the values:
+// S2 <= (1 + n) M2, n <= TB, so S2 - S1^2 / n loses at most 8 bits of 53; a
+// constant row gives exactly 0; a NaN or infinite first value is no pivot --
+// inf - inf would turn an infinite mean into NaN -- and K is 0 there, so NaN
+// and inf reach the sums as the values themselves); the lane sums of two rows add over each
+// 16-lane segment by DPP (pair_fold16), the segments' (S1, S2) are staged in
+// LDS, and after the tile's last barrier 3 * TA threads add them in segment
+// order, finish them and store the three planes, TA consecutive doubles each.
+// With moments the TransDesc counts the destination in rows: da and the batch
+// dims' destination strides are in units of the row pitch, so a tile row's
+// result row is dof + a * da and its first element is that times pitch.
+struct MomOut {
+  double *parts;
+  int64_t nrows;   // rows of the result (plane length)
+  int64_t pitch;   // elements between the result's row starts
+};
+struct NoMom {};
+
+// Two tile rows' lane sums a, b -> the sums over the 16 lanes of a DPP row:
+// lanes 0-7 end with a's, lanes 8-15 with b's.  row_mirror pairs lane i with
+// 15 - i while every lane still holds both values, so each lane keeps one row
+// and hands the other over; the partners of the next steps (row_half_mirror,
+// lane ^ 2, lane ^ 1) hold the same row.  16 VALU operations per pair against
+// 36 per row for two full wave folds.  Plain adds commute: every lane of a
+// half ends with the same bits.
+__device__ __forceinline__ double pair_fold16(double a, double b, int lane) {
+  const bool hi = lane & 8;
+  double v = (hi ? b : a) + dpp_mov<0x140>(hi ? a : b);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0xB1>(v);
+  return v;
+}
+
+template <typename T, int TA, int TB, int VA, int VB, bool FUSED = false, typename F = void>
 __global__ void __launch_bounds__(kThreads)
-    k_transpose(const T *__restrict__ src, T *__restrict__ dst, TransDesc d) {
+    k_transpose(const T *__restrict__ src, T *__restrict__ dst, TransDesc d,
+                typename std::conditional<std::is_void<F>::value, NoMom, MomOut>::type mo) {
   __shared__ T tile[TB][TA + 1];
   constexpr int NVA = TA / VA;
   constexpr int RPA = kThreads / NVA;
@@ -194,6 +243,14 @@ __global__ void __launch_bounds__(kThreads)
   const int ux = threadIdx.x % NVB, uy = threadIdx.x / NVB;
   const int ia = tx * VA;
   const int ib = ux * VB;
+  constexpr bool MOM = !std::is_void<F>::value;
+  constexpr int NSEG = NVB / 16;  // 16-lane segments (DPP rows) of a tile row
+  static_assert(!MOM || (!FUSED && sizeof(typename std::conditional<MOM, F, T>::type) == sizeof(T) &&
+                         VA * sizeof(T) == 16 && VB * sizeof(T) == 16 && NVB % 16 == 0 && NS % 2 == 0 &&
+                         3 * TA <= kThreads),
+                "moments: vectorised unfused tiles of float / double only");
+  __shared__ double mst[MOM ? (2 * NSEG + 1) * TA : 1];  // S1[TA][NSEG], S2[TA][NSEG], K[TA]
+  double p1 = 0.0, p2 = 0.0, pK = 0.0;  // the even row of a pair
 
   for (uint64_t t = blockIdx.x; t < d.ntiles; t += gridDim.x) {
     // consecutive blocks walk dim b (the destination-contiguous one): their
@@ -239,26 +296,77 @@ __global__ void __launch_bounds__(kThreads)
     __syncthreads();
 
     // store: lanes walk dim b (destination-contiguous)
-    T *q = dst + dof + b0;
+    T *q = dst + b0;
+    if constexpr (!MOM) q += dof;
     const bool fullB = (b0 + ib + VB <= d.Lb);
 #pragma unroll
     for (int it = 0; it < NS; ++it) {
       const int ra = uy + it * RPB;
-      if (a0 + ra < d.La) {
+      // (moments: every lane runs the fold, also those of rows past La)
+      if (MOM || a0 + ra < d.La) {
         T w[VB];
 #pragma unroll
         for (int k = 0; k < VB; ++k) w[k] = tile[ib + k][ra];
-        T *p = q + arow<FUSED>(d, a0 + ra) + ib;
-        if (fullB) {
-          vstore_nt<T, VB>(p, w);
-        } else {
+        if (!MOM || a0 + ra < d.La) {
+          T *p = q + ib;
+          if constexpr (MOM) p += (dof + (a0 + ra) * d.da) * mo.pitch;
+          else p += arow<FUSED>(d, a0 + ra);
+          if (fullB) {
+            vstore_nt<T, VB>(p, w);
+          } else {
 #pragma unroll
-          for (int k = 0; k < VB; ++k)
-            if (b0 + ib + k < d.Lb) p[k] = w[k];
+            for (int k = 0; k < VB; ++k)
+              if (b0 + ib + k < d.Lb) p[k] = w[k];
+          }
+        }
+        if constexpr (MOM) {
+          const double K0 = (double)__builtin_bit_cast(F, tile[0][ra]);
+          const double K = K0 - K0 == 0.0 ? K0 : 0.0;  // finite, else 0
+          double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+          for (int k = 0; k < VB; ++k) {
+            const double y = b0 + ib + k < d.Lb ? (double)__builtin_bit_cast(F, w[k]) - K : 0.0;
+            s1 += y;
+            s2 = fma(y, y, s2);
+          }
+          if ((it & 1) == 0) {
+            p1 = s1;
+            p2 = s2;
+            pK = K;
+          } else {
+            const int lane = threadIdx.x & 63;
+            s1 = pair_fold16(p1, s1, lane);
+            s2 = pair_fold16(p2, s2, lane);
+            if ((lane & 7) == 0) {  // lane 0 of a segment: the even row, lane 8: the odd one
+              const int rr = (lane & 8) ? ra : ra - RPB, seg = ux / 16;
+              mst[rr * NSEG + seg] = s1;
+              mst[(TA + rr) * NSEG + seg] = s2;
+              if (seg == 0) mst[2 * TA * NSEG + rr] = (lane & 8) ? K : pK;
+            }
+          }
         }
       }
     }
     __syncthreads();
+    if constexpr (MOM) {
+      // the next tile's sums are staged only after its load barrier, which
+      // these threads have not passed yet
+      const int r = threadIdx.x % TA, plane = threadIdx.x / TA;
+      if (plane < 3 && a0 + r < d.La) {
+        double S1 = 0.0, S2 = 0.0;
+#pragma unroll
+        for (int g = 0; g < NSEG; ++g) {
+          S1 += mst[r * NSEG + g];
+          S2 += mst[(TA + r) * NSEG + g];
+        }
+        const double n = (double)min((int64_t)TB, d.Lb - b0);
+        const double m1 = S1 / n;
+        const double m2 = fma(-S1, m1, S2);
+        const int64_t row = dof + (a0 + r) * d.da;
+        mo.parts[((int64_t)tb * 3 + plane) * mo.nrows + row] =
+            plane == 0 ? mst[2 * TA * NSEG + r] : plane == 1 ? m1 : (m2 > 0.0 ? m2 : 0.0);
+      }
+    }
   }
 }
 
@@ -665,18 +773,18 @@ void launch_transpose_tile(const T *src, T *dst, const TransDesc &td, bool va_ve
   constexpr int W = 16 / (int)sizeof(T);
   if constexpr (sizeof(T) >= 4) {
     if (fused) {  // fused axis pairs: vectorised only (the host fuses aligned layouts)
-      k_transpose<T, TA, TB, W, W, true><<<grid, kThreads, 0, st>>>(src, dst, td);
+      k_transpose<T, TA, TB, W, W, true><<<grid, kThreads, 0, st>>>(src, dst, td, NoMom{});
       return;
     }
   }
   if (va_vec && vb_vec)
-    k_transpose<T, TA, TB, W, W><<<grid, kThreads, 0, st>>>(src, dst, td);
+    k_transpose<T, TA, TB, W, W><<<grid, kThreads, 0, st>>>(src, dst, td, NoMom{});
   else if (va_vec)
-    k_transpose<T, TA, TB, W, 1><<<grid, kThreads, 0, st>>>(src, dst, td);
+    k_transpose<T, TA, TB, W, 1><<<grid, kThreads, 0, st>>>(src, dst, td, NoMom{});
   else if (vb_vec)
-    k_transpose<T, TA, TB, 1, W><<<grid, kThreads, 0, st>>>(src, dst, td);
+    k_transpose<T, TA, TB, 1, W><<<grid, kThreads, 0, st>>>(src, dst, td, NoMom{});
   else
-    k_transpose<T, TA, TB, 1, 1><<<grid, kThreads, 0, st>>>(src, dst, td);
+    k_transpose<T, TA, TB, 1, 1><<<grid, kThreads, 0, st>>>(src, dst, td, NoMom{});
 }
 
 // Tile shapes per element size (TA x TB elements).  Measured on the C2 swap
@@ -721,6 +829,48 @@ int launch_transpose_t(const T *src, T *dst, const TransDesc &td, Tile tl, bool 
   return BM_E_ARG;
 }
 
+// bm_copy_strided_moments: what the caller asks for and what the transpose
+// path answers.  The moments kernels exist for the tiles float32 / float64
+// pick on b axes of 64 elements and more, and float64 on 32 and more
+// (mom_tile: the tiles with at least 16 lanes per tile row); every other tile, the
+// fused axis pairs and the element-wise tails report "not fused".
+struct MomReq {
+  int dt;                  // BM_F32 / BM_F64
+  int64_t R, pitch, nrows; // the result's rows
+  double *parts;           // workspace: [ntB][3][nrows]
+  size_t parts_bytes;
+  bool plan_only;          // size the workspace only, launch nothing
+  int fused;               // out: the moments kernel ran (plan_only: would run)
+  int64_t ntB, TB;         // out: parts and values per full part
+};
+
+bool mom_tile(int es, Tile tl) {
+  constexpr Tile k4[] = {{64, 256}, {32, 256}, {16, 256}, {64, 64}, {64, 128}, {32, 64}};
+  constexpr Tile k8[] = {{32, 256}, {32, 64}, {64, 32}, {16, 128}};
+  const Tile *c = es == 4 ? k4 : k8;
+  const int n = es == 4 ? (int)(sizeof(k4) / sizeof(Tile)) : (int)(sizeof(k8) / sizeof(Tile));
+  for (int i = 0; i < n; ++i)
+    if (c[i].ta == tl.ta && c[i].tb == tl.tb) return true;
+  return false;
+}
+
+template <typename T, typename F>
+int launch_transpose_mom(const T *src, T *dst, const TransDesc &td, Tile tl, const MomOut &mo, hipStream_t st) {
+  constexpr int W = 16 / (int)sizeof(T);
+  uint64_t g = td.ntiles;
+  if (g > kMaxGrid) g = kMaxGrid;
+#define BM_TILE(A, B) \
+  if (tl.ta == A && tl.tb == B) { k_transpose<T, A, B, W, W, false, F><<<(int)g, kThreads, 0, st>>>(src, dst, td, mo); return BM_OK; }
+  if constexpr (sizeof(T) == 4) {
+    BM_TILE(64, 256) BM_TILE(32, 256) BM_TILE(16, 256) BM_TILE(64, 64) BM_TILE(64, 128) BM_TILE(32, 64)
+  } else {
+    BM_TILE(32, 256) BM_TILE(32, 64) BM_TILE(64, 32) BM_TILE(16, 128)
+  }
+#undef BM_TILE
+  bm_set_error("bm_copy_strided_moments: no moments tile %dx%d", tl.ta, tl.tb);
+  return BM_E_ARG;
+}
+
 // Relative cost of a tile row segment of n bytes (1.0 = the fastest shape),
 // from the same sweep: short segments waste DRAM bursts.
 double seg_cost_read(int64_t n) { return n >= 256 ? 1.0 : n >= 128 ? 1.02 : n >= 64 ? 1.25 : 1.6; }
@@ -752,7 +902,7 @@ Tile pick_tile(int64_t La, int64_t Lb, int es) {
 }
 
 int launch_transpose(const char *src, char *dst, const std::vector<Dim> &dims, int a, int es,
-                     hipStream_t st, bool allow_fuse = true) {
+                     hipStream_t st, bool allow_fuse = true, MomReq *mr = nullptr) {
   const int b = (int)dims.size() - 1;
   std::vector<Dim> batch;
   for (int k = 0; k < (int)dims.size(); ++k)
@@ -827,7 +977,36 @@ int launch_transpose(const char *src, char *dst, const std::vector<Dim> &dims, i
   }
   if (fused && !(va && vb && (td.Lb1.d * es) % 16 == 0 && (td.La1.d * es) % 16 == 0)) {
     // the fused kernels are vectorised only: the plain tiles handle it
-    return launch_transpose(src, dst, dims, a, es, st, false);
+    return launch_transpose(src, dst, dims, a, es, st, false, mr);
+  }
+  if (mr) {
+    // moments ride on the unfused vectorised tiles whose rows along b are the
+    // result's rows: row index = destination offset / pitch, below nrows
+    bool ok = !fused && va && vb && ((es == 4 && mr->dt == BM_F32) || (es == 8 && mr->dt == BM_F64)) &&
+              td.Lb == mr->R && ntB <= 256 && mom_tile(es, tl) && td.da % mr->pitch == 0;
+    int64_t top = (td.La - 1) * td.da;  // the last row's offset
+    for (const Dim &x : batch) {
+      if (x.ds % mr->pitch) ok = false;
+      top += (x.n - 1) * x.ds;
+    }
+    if (ok && top / mr->pitch >= mr->nrows) ok = false;
+    if (ok) {
+      mr->fused = 1;
+      mr->ntB = (int64_t)ntB;
+      mr->TB = TB;
+      if (mr->plan_only) return BM_OK;
+      const size_t need = (size_t)ntB * 3 * (size_t)mr->nrows * 8;
+      if (!mr->parts || mr->parts_bytes < need) {
+        bm_set_error("bm_copy_strided_moments: workspace too small (%zu < %zu)", mr->parts_bytes, need);
+        return BM_E_WS;
+      }
+      const MomOut mo{mr->parts, mr->nrows, mr->pitch};
+      td.da /= mr->pitch;  // the destination in rows (MomOut)
+      for (int k = 0; k < td.batch.n; ++k) td.batch.ds[k] /= mr->pitch;
+      return es == 4 ? launch_transpose_mom<uint32_t, float>((const uint32_t *)src, (uint32_t *)dst, td, tl, mo, st)
+                     : launch_transpose_mom<uint64_t, double>((const uint64_t *)src, (uint64_t *)dst, td, tl, mo, st);
+    }
+    if (mr->plan_only) return BM_OK;
   }
   if (va && vb && (es == 1 || es == 2)) {
     // packed-word tiles: 256-B (u16) / 128-B (u8) source and 1-KiB destination segments
@@ -958,11 +1137,10 @@ std::vector<Dim> canonicalize(std::vector<Dim> dims) {
   return out;
 }
 
-}  // namespace
-
-extern "C" int bm_copy_strided(const void *src_, void *dst_, int ndim, const int64_t *shape,
-                               const int64_t *src_strides, const int64_t *dst_strides,
-                               int elem_bytes, void *stream) {
+// bm_copy_strided's body; with ``mr`` the transpose path may run the moments
+// kernels (mr->fused), or only plan them (mr->plan_only: nothing is launched)
+int copy_strided(const void *src_, void *dst_, int ndim, const int64_t *shape, const int64_t *src_strides,
+                 const int64_t *dst_strides, int elem_bytes, void *stream, MomReq *mr) {
   if (ndim < 0 || ndim > 24 || elem_bytes <= 0 || (ndim > 0 && (!shape || !src_strides || !dst_strides))) {
     bm_set_error("bm_copy_strided: bad arguments (ndim=%d elem_bytes=%d)", ndim, elem_bytes);
     return BM_E_ARG;
@@ -976,7 +1154,8 @@ extern "C" int bm_copy_strided(const void *src_, void *dst_, int ndim, const int
     if (shape[k] == 0) return BM_OK;  // empty: nothing to move
     dims.push_back({shape[k], src_strides[k], dst_strides[k]});
   }
-  if (!src_ || !dst_) {
+  const bool plan_only = mr && mr->plan_only;
+  if (!plan_only && (!src_ || !dst_)) {
     bm_set_error("bm_copy_strided: null pointer");
     return BM_E_ARG;
   }
@@ -994,15 +1173,16 @@ extern "C" int bm_copy_strided(const void *src_, void *dst_, int ndim, const int
   char *dst = (char *)dst_;
   int rc;
   const Dim &in = c.back();
+  int a = -1;
+  if (!(in.ss == 1 && in.ds == 1) && in.ds == 1 && es <= 8)
+    for (int k = (int)c.size() - 2; k >= 0; --k)
+      if (c[k].ss == 1) { a = k; break; }
+  if (plan_only) return a >= 0 ? launch_transpose(src, dst, c, a, es, st, true, mr) : BM_OK;
   if (in.ss == 1 && in.ds == 1) {
     rc = try_transpose_runs(src, dst, c, es, st) == 0 ? BM_OK : launch_rowcopy(src, dst, c, es, st);
   } else {
-    int a = -1;
-    if (in.ds == 1 && es <= 8)
-      for (int k = (int)c.size() - 2; k >= 0; --k)
-        if (c[k].ss == 1) { a = k; break; }
     if (a >= 0) {
-      rc = launch_transpose(src, dst, c, a, es, st);
+      rc = launch_transpose(src, dst, c, a, es, st, true, mr);
     } else if (es == 16 && in.ds == 1) {
       // 16-B elements that need a transpose: move as pairs of 8-B words
       for (Dim &x : c) { x.ss *= 2; x.ds *= 2; }
@@ -1018,6 +1198,104 @@ extern "C" int bm_copy_strided(const void *src_, void *dst_, int ndim, const int
     bm_set_error("bm_copy_strided: launch failed: %s", hipGetErrorString(e));
     return BM_E_HIP;
   }
+  return BM_OK;
+}
+
+// the checks bm_copy_strided_moments and its workspace query share
+int check_moments_args(const char *who, int ndim, const int64_t *shape, int elem_bytes, int in_dtype, int64_t R,
+                       int64_t row_pitch, int64_t nrows) {
+  if (in_dtype != BM_F32 && in_dtype != BM_F64) {
+    bm_set_error("%s: in_dtype %d is not float32 / float64", who, in_dtype);
+    return BM_E_ARG;
+  }
+  if (elem_bytes != (in_dtype == BM_F32 ? 4 : 8)) {
+    bm_set_error("%s: elem_bytes %d does not fit in_dtype %d", who, elem_bytes, in_dtype);
+    return BM_E_ARG;
+  }
+  if (R < 1 || nrows < 1 || row_pitch < R) {
+    bm_set_error("%s: bad rows (R=%lld row_pitch=%lld nrows=%lld; R, nrows >= 1 and row_pitch >= R)", who,
+                 (long long)R, (long long)row_pitch, (long long)nrows);
+    return BM_E_ARG;
+  }
+  if (ndim < 1 || ndim > 24 || !shape) {
+    bm_set_error("%s: bad arguments (ndim=%d)", who, ndim);
+    return BM_E_ARG;
+  }
+  unsigned __int128 total = 1;
+  for (int k = 0; k < ndim; ++k) {
+    if (shape[k] < 0) {
+      bm_set_error("%s: negative shape at dim %d", who, k);
+      return BM_E_ARG;
+    }
+    total *= (unsigned __int128)shape[k];
+    if (total > ((unsigned __int128)1 << 62)) total = (unsigned __int128)1 << 62;
+  }
+  if (total != (unsigned __int128)R * (unsigned __int128)nrows) {
+    bm_set_error("%s: the copy's elements do not make nrows=%lld rows of R=%lld", who, (long long)nrows,
+                 (long long)R);
+    return BM_E_ARG;
+  }
+  return BM_OK;
+}
+
+}  // namespace
+
+extern "C" int bm_copy_strided(const void *src, void *dst, int ndim, const int64_t *shape,
+                               const int64_t *src_strides, const int64_t *dst_strides,
+                               int elem_bytes, void *stream) {
+  return copy_strided(src, dst, ndim, shape, src_strides, dst_strides, elem_bytes, stream, nullptr);
+}
+
+extern "C" int bm_copy_strided_moments_workspace_bytes(int ndim, const int64_t *shape, const int64_t *src_strides,
+                                                       const int64_t *dst_strides, int elem_bytes, int in_dtype,
+                                                       int64_t R, int64_t row_pitch, int64_t nrows,
+                                                       size_t *bytes) {
+  const char *who = "bm_copy_strided_moments_workspace_bytes";
+  if (!bytes) { bm_set_error("%s: null out", who); return BM_E_ARG; }
+  int rc = check_moments_args(who, ndim, shape, elem_bytes, in_dtype, R, row_pitch, nrows);
+  if (rc) return rc;
+  MomReq mr{};
+  mr.dt = in_dtype;
+  mr.R = R;
+  mr.pitch = row_pitch;
+  mr.nrows = nrows;
+  mr.plan_only = true;
+  rc = copy_strided(nullptr, nullptr, ndim, shape, src_strides, dst_strides, elem_bytes, nullptr, &mr);
+  if (rc) return rc;
+  *bytes = mr.fused ? (size_t)mr.ntB * 3 * (size_t)nrows * 8 : 0;
+  return BM_OK;
+}
+
+extern "C" int bm_copy_strided_moments(const void *src, void *dst, int ndim, const int64_t *shape,
+                                       const int64_t *src_strides, const int64_t *dst_strides, int elem_bytes,
+                                       int in_dtype, int64_t R, int64_t row_pitch, int64_t nrows,
+                                       void *workspace, size_t workspace_bytes, void *state, size_t state_bytes,
+                                       int *fused, void *stream) {
+  const char *who = "bm_copy_strided_moments";
+  if (!fused || !state) { bm_set_error("%s: null state / fused", who); return BM_E_ARG; }
+  *fused = 0;
+  int rc = check_moments_args(who, ndim, shape, elem_bytes, in_dtype, R, row_pitch, nrows);
+  if (rc) return rc;
+  size_t need = 0;
+  rc = bm_reduce_state_bytes(BM_STAT_VAR, in_dtype, nrows, &need);
+  if (rc) return rc;
+  if (state_bytes < need) {
+    bm_set_error("%s: state too small (%zu < %zu)", who, state_bytes, need);
+    return BM_E_ARG;
+  }
+  MomReq mr{};
+  mr.dt = in_dtype;
+  mr.R = R;
+  mr.pitch = row_pitch;
+  mr.nrows = nrows;
+  mr.parts = (double *)workspace;
+  mr.parts_bytes = workspace_bytes;
+  rc = copy_strided(src, dst, ndim, shape, src_strides, dst_strides, elem_bytes, stream, &mr);
+  if (rc || !mr.fused) return rc;
+  // the b-tiles' partial states, in tile order, into the one two-plane state
+  rc = bm_merge_tile_moments(mr.parts, mr.ntB, mr.TB, R, nrows, (double *)state, (hipStream_t)stream);
+  if (rc) return rc;
+  *fused = 1;
   return BM_OK;
 }
 

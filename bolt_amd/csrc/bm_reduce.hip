@@ -1549,7 +1549,49 @@ int run_reduce(int stat, const void *src, int dt, int64_t O, int64_t R, int64_t 
   return check_launch(who);
 }
 
+// The b-tile states of a moments transpose (bm_copy_strided_moments) -> the
+// BM_STAT_VAR state of every row.  Part p holds three planes of nrows: the
+// tile's pivot K (one of the row's values), mean - K and M2, over tb values
+// (the last part: the rest of R).  chan over the parts in tile order, in the
+// frame shifted by the first tile's pivot, as the rows kernel keeps its
+// Welford state around the row's first element: K_p - K_0 is exact for offset
+// data.  The pivots are finite (a tile whose first value is not takes 0), so
+// an infinity or NaN of the row is in its tile's mean - K alone.  A row with
+// an infinity has an infinite tile mean, which chan's delta turns into NaN
+// when a finite tile follows; its mean is then the sum of the tile means
+// (inf, or NaN for inf - inf or a NaN tile), what a sum over the row gives.
+__global__ void __launch_bounds__(kThreads)
+    k_red_merge_tiles(const double *__restrict__ parts, int64_t nparts, int64_t tb, int64_t R, int64_t nrows,
+                      double *__restrict__ state) {
+  const int64_t step = (int64_t)gridDim.x * kThreads;
+  for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < nrows; e += step) {
+    const double K0 = parts[e];
+    double n = 0.0, m = 0.0, q = 0.0;
+    for (int64_t p = 0; p < nparts; ++p) {
+      const double nb = (double)(min(R, (p + 1) * tb) - p * tb);
+      const double *pp = parts + 3 * p * nrows + e;
+      chan(n, m, q, nb, (pp[0] - K0) + pp[nrows], pp[2 * nrows], true);
+    }
+    m += K0;
+    if (m != m) {
+      double s = 0.0;
+      for (int64_t p = 0; p < nparts; ++p) s += parts[3 * p * nrows + e] + parts[(3 * p + 1) * nrows + e];
+      m = s;
+    }
+    state[e] = m;
+    state[nrows + e] = q > 0.0 ? q : 0.0;
+  }
+}
+
 }  // namespace
+
+int bm_merge_tile_moments(const double *parts, int64_t nparts, int64_t tb, int64_t R, int64_t nrows,
+                          double *state, hipStream_t stream) {
+  int64_t g = cdiv(nrows, kThreads);
+  if (g > 4096) g = 4096;
+  k_red_merge_tiles<<<(int)g, kThreads, 0, stream>>>(parts, nparts, tb, R, nrows, state);
+  return check_launch("bm_copy_strided_moments");
+}
 
 extern "C" int bm_reduce_workspace_bytes(int stat, int in_dtype, int64_t O, int64_t R, int64_t I,
                                          size_t *bytes) {

@@ -29,6 +29,13 @@ SIGNATURES = {
     "bm_host_writable": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_int)]),
     "bm_copy_strided": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _i64p, _i64p, _i64p,
                                    _c.c_int, _c.c_void_p]),
+    "bm_copy_strided_moments_workspace_bytes": (_c.c_int, [_c.c_int, _i64p, _i64p, _i64p, _c.c_int, _c.c_int,
+                                                           _c.c_int64, _c.c_int64, _c.c_int64,
+                                                           _c.POINTER(_c.c_size_t)]),
+    "bm_copy_strided_moments": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _i64p, _i64p, _i64p, _c.c_int,
+                                           _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
+                                           _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_int),
+                                           _c.c_void_p]),
     "bm_permute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _i64p,
                               _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p]),
     "bm_gather_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64,

@@ -131,6 +131,7 @@ class HipBackend(object):
         self._args = {}  # (shape, perm) -> ctypes arguments of bm_permute
         self._cargs = {}  # (shape, strides, strides) -> ctypes arrays of bm_copy_strided
         self._ws = {}    # reduction -> workspace bytes
+        self._margs = {}  # copy with moments -> ctypes arrays of bm_copy_strided_moments + its workspace bytes
 
     # Pointer and stream arguments go to ctypes as plain ints (the argtypes
     # are c_void_p): no c_void_p object per argument on the launch path.
@@ -149,8 +150,20 @@ class HipBackend(object):
                    "bm_host_writable")
         return bool(ok.value)
 
-    def copy_strided(self, src, src_off, dst, dst_off, shape, sstrides, dstrides, es):
-        """dst[dst_off + idx . dstrides] = src[src_off + idx . sstrides] (offsets in bytes)."""
+    # copy_strided takes ``moments=`` (bm_copy_strided_moments): array.py asks
+    # for it only of a backend with this attribute
+    fuses_swap_moments = True
+
+    def copy_strided(self, src, src_off, dst, dst_off, shape, sstrides, dstrides, es, moments=None):
+        """dst[dst_off + idx . dstrides] = src[src_off + idx . sstrides] (offsets in bytes).
+
+        ``moments`` = (dtype code, R, pitch, rows, state): the destination is
+        ``rows`` rows of R elements, ``pitch`` elements apart; where the copy
+        is a tile transpose along them it also leaves their STAT_VAR state in
+        ``state`` -> True if it did (bm_copy_strided_moments; else the plain
+        copy, ``state`` untouched)."""
+        if moments is not None:
+            return self._copy_moments(src, src_off, dst, dst_off, shape, sstrides, dstrides, es, moments)
         nd = len(shape)
         if nd == 0:
             shape, sstrides, dstrides, nd = [1], [1], [1], 1
@@ -167,6 +180,42 @@ class HipBackend(object):
                                       args[0], args[1], args[2], int(es), self._stream(src))
         if rc:
             _lib.check(rc, "bm_copy_strided")
+
+    def copy_moments_plan(self, shape, sstrides, dstrides, es, code, R, pitch, rows):
+        """(ctypes shape, source strides, destination strides, workspace bytes)
+        of a copy_strided with ``moments=``, cached; 0 workspace bytes: the
+        library would not fuse this copy (bm_copy_strided_moments_workspace_bytes)."""
+        key = (tuple(shape), tuple(sstrides), tuple(dstrides), int(es), code, R, pitch, rows)
+        args = self._margs.get(key)
+        if args is None:
+            a = (_lib.i64_array(shape), _lib.i64_array(sstrides), _lib.i64_array(dstrides))
+            n = ctypes.c_size_t(0)
+            _lib.check(self.lib.bm_copy_strided_moments_workspace_bytes(len(shape), a[0], a[1], a[2], int(es), code,
+                                                                        R, pitch, rows, ctypes.byref(n)),
+                       "bm_copy_strided_moments_workspace_bytes")
+            args = a + (n.value,)
+            if len(self._margs) > 4096:
+                self._margs.clear()
+            self._margs[key] = args
+        return args
+
+    def _copy_moments(self, src, src_off, dst, dst_off, shape, sstrides, dstrides, es, moments):
+        import torch
+        code, R, pitch, rows, state = moments
+        args = self.copy_moments_plan(shape, sstrides, dstrides, es, code, R, pitch, rows)
+        nws = args[3]
+        # the tiles' partial states: read by the merge kernel of the same
+        # call, on the same stream, so the block may go back to the allocator
+        ws = torch.empty(nws, dtype=torch.uint8, device=src.device) if nws else None
+        fused = ctypes.c_int(0)
+        rc = self.lib.bm_copy_strided_moments(self._ptr(src, src_off), self._ptr(dst, dst_off), len(shape),
+                                              args[0], args[1], args[2], int(es), code, R, pitch, rows,
+                                              ws.data_ptr() if ws is not None else None, nws,
+                                              state.data_ptr(), state.numel() * state.element_size(),
+                                              ctypes.byref(fused), self._stream(src))
+        if rc:
+            _lib.check(rc, "bm_copy_strided_moments")
+        return bool(fused.value)
 
     def permute(self, src, shape, perm, es, dst):
         key = (tuple(shape), tuple(perm))

@@ -236,6 +236,21 @@ _KEEP_STATE_DIV = 64
 # the run that measured it, and the tests of the column branches.
 _KEEP_COLS = False
 
+# swap(), then mean() / var() / std() over the last axis of the result (time
+# series keyed by time, swapped to key = voxel, then per-voxel statistics):
+# on one GPU the swap's transpose kernel also leaves the STAT_VAR state of
+# every result row (bm_copy_strided_moments), remembered for the axes
+# (ndim - 1,) like a kept state, and all three statistics -- the mean too --
+# are finished from it without reading the array.  Asked for only of float32 /
+# float64 swaps that move more bytes than _FUSE_SWAP_MIN_BYTES (the result
+# would be re-read from HBM, as for _KEEP_MIN_BYTES, which tests lower on its
+# own) and whose state is at most 1 / _FUSE_SWAP_STATE_DIV of them; the library
+# fuses only tile transposes along the result's rows and says so.
+# FUSE_SWAP_MOMENTS = False (BOLT_AMD_FUSE_SWAP_MOMENTS=0): the plain copy.
+FUSE_SWAP_MOMENTS = os.environ.get("BOLT_AMD_FUSE_SWAP_MOMENTS", "1") != "0"
+_FUSE_SWAP_MIN_BYTES = 256 << 20
+_FUSE_SWAP_STATE_DIV = 64
+
 _REDUCE_PLANS = {}  # (local shape, axes, stat, dtype, world) -> device reduction plan
 _MOMENT_PLANS = {}  # (local shape, axes, dtype, shape, world) -> device plan of stats() (one read, several moments)
 
@@ -563,14 +578,33 @@ class BoltArrayMI355X(BoltArray):
             if pp is not None:
                 P, rows, oshape, psstr, dstr = pp
                 pbuf = _empty(rows * P * es, src.device)
-                be.copy_strided(src, 0, pbuf, 0, oshape, psstr if sstr is None else sstr, dstr, es)
-                return self._derive_padded(pbuf, P, new_shape, split)
+                csstr = psstr if sstr is None else sstr
+                st = self._swap_state(be, src.device, new_shape, es, oshape, csstr, dstr, P)
+                if st is None:
+                    be.copy_strided(src, 0, pbuf, 0, oshape, csstr, dstr, es)
+                    return self._derive_padded(pbuf, P, new_shape, split)
+                fused = be.copy_strided(src, 0, pbuf, 0, oshape, csstr, dstr, es,
+                                        moments=(st[0], new_shape[-1], P, st[1], st[2]))
+                return self._derive_padded(pbuf, P, new_shape, split)._with_swap_state(st, fused)
+            dstr = _padded_strides(new_shape, new_shape[-1])
             if sstr is None:
+                # bm_permute's own strides: the same kernels, through the entry that takes the state
+                cstr = _padded_strides(self._shape, self._shape[-1])
+                csstr = [cstr[p] for p in perm]
+            else:
+                csstr = sstr
+            st = self._swap_state(be, src.device, new_shape, es, list(new_shape), csstr, dstr, new_shape[-1])
+            if sstr is None and st is None:
                 data = permute_sharded(self._ctx, be, src, self._shape, perm, es)
             else:
                 n = int(np.prod(new_shape, dtype=np.int64))
                 data = _empty(n * es, src.device)
-                be.copy_strided(src, 0, data, 0, list(new_shape), sstr, _padded_strides(new_shape, new_shape[-1]), es)
+                if st is None:
+                    be.copy_strided(src, 0, data, 0, list(new_shape), csstr, dstr, es)
+                else:
+                    fused = be.copy_strided(src, 0, data, 0, list(new_shape), csstr, dstr, es,
+                                            moments=(st[0], new_shape[-1], new_shape[-1], st[1], st[2]))
+                    return self._derive(data, new_shape, split)._with_swap_state(st, fused)
         else:
             # across GPUs: the exchange's pack reads a padded source in place
             # and its unpack writes the result's rows at the same pitch rule
@@ -584,6 +618,32 @@ class BoltArrayMI355X(BoltArray):
             if pp is not None:
                 return self._derive_padded(data, pp[0], new_shape, split)
         return self._derive(data, new_shape, split)
+
+    def _swap_state(self, be, dev, new_shape, es, oshape, sstr, dstr, pitch):
+        """(dtype code, rows, state buffer) for a one-GPU move into ``new_shape``
+        (the copy ``oshape`` / ``sstr`` / ``dstr``, rows ``pitch`` elements
+        apart) that should also leave its rows' STAT_VAR state, or None: the
+        rule is at FUSE_SWAP_MOMENTS, and the library's plan of the copy says
+        whether it can fuse at all before anything is allocated."""
+        if not FUSE_SWAP_MOMENTS or self._dtype.kind != 'f' or es not in (4, 8) or self._dtype.byteorder == '>' \
+                or len(new_shape) < 2 \
+                or not getattr(be, "fuses_swap_moments", False):
+            return None
+        rows = int(np.prod(new_shape[:-1], dtype=np.int64))
+        nbytes = rows * new_shape[-1] * es
+        if not rows or nbytes <= _FUSE_SWAP_MIN_BYTES or 16 * rows > nbytes // _FUSE_SWAP_STATE_DIV:
+            return None
+        code = dtype_code(self._dtype)
+        if not be.copy_moments_plan(oshape, sstr, dstr, es, code, new_shape[-1], pitch, rows)[3]:
+            return None
+        return code, rows, _empty(be.state_bytes(_lib.STAT_VAR, code, rows), dev)
+
+    def _with_swap_state(self, st, fused):
+        """Remember the state a move left (``fused``) for the last axis; the
+        mark lets mean() be served from it too (see _reduced)."""
+        if fused:
+            self.__dict__["_kept"] = {(len(self._shape) - 1,): (st[2], self._shape[-1], st[1], None, True)}
+        return self
 
     def _pitch_of(self, mv, es):
         """The pitched copy plan of move ``mv`` (cached, see _pitch_plan), or
@@ -1157,6 +1217,9 @@ class BoltArrayMI355X(BoltArray):
         held = self.__dict__.get("_kept")
         if held and KEEP_MOMENTS and stat in (_lib.STAT_VAR, _lib.STAT_STD) and tuple(axset) in held:
             return self._from_kept(held[tuple(axset)], stat, code, ocode, out_dtype, out_shape), out_dtype
+        if held and stat in _MOMENTS and len(held.get(tuple(axset), ())) > 4:
+            # a state left by the swap's transpose (_with_swap_state) serves the mean too
+            return self._from_kept(held[tuple(axset)], stat, code, ocode, out_dtype, out_shape), out_dtype
         pbuf = self.__dict__.get("_pbuf")
         if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and ctx.world_size > 1 \
                 and 0 not in axset:
@@ -1294,7 +1357,7 @@ class BoltArrayMI355X(BoltArray):
     def _from_kept(self, entry, stat, code, ocode, out_dtype, out_shape):
         """var / std finished from a kept state: one reduce_combine of one part
         into the host result of the branch that kept it, no read of the array."""
-        state, count, nlaunch, drop = entry
+        state, count, nlaunch, drop = entry[:4]
         dev = state.device
         be = backend_for(dev)
         shape = out_shape if drop is None else drop[:3]

@@ -115,6 +115,45 @@ int bm_copy_strided(const void *src, void *dst, int ndim, const int64_t *shape,
                     int elem_bytes, void *stream);
 
 /*
+ * bm_copy_strided_moments -- bm_copy_strided of a float32 / float64 array
+ * whose destination is `nrows` rows of `R` elements, `row_pitch` (>= R)
+ * elements apart, which also leaves the BM_STAT_VAR state of every row
+ * (mean[nrows] then M2[nrows], float64: what bm_reduce_state(BM_STAT_VAR)
+ * of the written rows gives, from other arithmetic) in `state`, so that a
+ * later mean / var / std over the rows is
+ *   bm_reduce_combine(stat, in_dtype, state, counts = {R}, nparts = 1, nrows, ...)
+ * and does not read the array again (swap, then statistics over the moved
+ * key axis: array.py:716-763 followed by _stat, array.py:284-334).
+ *
+ * The state is written (*fused = 1) only when the copy is a tile transpose
+ * on 16-B vectors whose destination-contiguous dim is the row itself (its
+ * extent is R), every row starts at a multiple of row_pitch elements below
+ * nrows * row_pitch, and the row spans at most 256 tiles; the transpose
+ * kernel then emits the state of every (row, tile) -- a pivot, mean - pivot
+ * and M2, float64 -- into `workspace` and a merge kernel combines them in
+ * tile order.  In every other case the call is
+ * exactly bm_copy_strided: *fused = 0 and `state` is not touched.  The bytes
+ * written to dst are bm_copy_strided's in both cases.
+ * workspace: bm_copy_strided_moments_workspace_bytes of the same arguments
+ * (0: this copy never fuses; the pointer may then be NULL).  state_bytes >=
+ * bm_reduce_state_bytes(BM_STAT_VAR, in_dtype, nrows).
+ * BM_E_ARG, before anything is launched: in_dtype not BM_F32 / BM_F64 or
+ * elem_bytes not its size, state or fused NULL, state_bytes too small,
+ * row_pitch < R, or prod(shape) != nrows * R.  BM_E_WS: the copy fuses and
+ * the workspace is too small.
+ */
+int bm_copy_strided_moments_workspace_bytes(int ndim, const int64_t *shape,
+                                            const int64_t *src_strides,
+                                            const int64_t *dst_strides, int elem_bytes,
+                                            int in_dtype, int64_t R, int64_t row_pitch,
+                                            int64_t nrows, size_t *bytes);
+int bm_copy_strided_moments(const void *src, void *dst, int ndim, const int64_t *shape,
+                            const int64_t *src_strides, const int64_t *dst_strides,
+                            int elem_bytes, int in_dtype, int64_t R, int64_t row_pitch,
+                            int64_t nrows, void *workspace, size_t workspace_bytes,
+                            void *state, size_t state_bytes, int *fused, void *stream);
+
+/*
  * bm_permute -- dst = ascontiguousarray(src.transpose(perm)) for a
  * C-contiguous src of `shape`.  This is BoltArraySpark.swap
  * (bolt/spark/array.py:716-763) and .transpose / .T / .swapaxes
