@@ -29,14 +29,14 @@ import os
 
 import numpy as np
 
-from bolt_amd.mi355x import _lib
+from bolt_amd.mi355x import _lib, reduction
 from bolt_amd.mi355x._ops import backend_for, dtype_code
 from bolt_amd.base import BoltArray
 from bolt_amd.mi355x.context import local_shape
 from bolt_amd.mi355x.dist import all_gather_bytes, concat_rows_sharded, gather_to_host, permute_sharded, redistribute_rows, select_sharded, _empty
-from bolt_amd.mi355x.transfer import SMALL as HOST_RESULT_MAX, finish_host_result, host_result, to_device, to_host
+from bolt_amd.mi355x.transfer import to_device, to_host
 from bolt_amd.local import BoltArrayLocal
-from bolt_amd.mi355x.plan import getplan, check_plan, padded_strides, swap_perm, swap_shape, reduce_layout, stat_dtype
+from bolt_amd.mi355x.plan import getplan, check_plan, padded_strides, swap_perm, swap_shape, reduce_layout
 from bolt_amd.utils import tupleize, argpack, inshape, istransposeable, isreshapeable
 
 _STAT_CODES = {'mean': _lib.STAT_MEAN, 'variance': _lib.STAT_VAR, 'stdev': _lib.STAT_STD}
@@ -77,10 +77,9 @@ def _tree(func, recs):
             nxt = torch.cat([nxt, recs[n - 1:].to(nxt.dtype)])
         recs = nxt
     return recs[0]
-# reductions whose result keeps the input dtype (numpy's same-dtype ufunc rule)
-_MOMENTS = (_lib.STAT_MEAN, _lib.STAT_VAR, _lib.STAT_STD)
-_KEEP_DTYPE = (_lib.STAT_SUM, _lib.STAT_MAX, _lib.STAT_MIN, _lib.STAT_PROD, _lib.STAT_BAND,
-               _lib.STAT_BOR, _lib.STAT_BXOR, _lib.STAT_FMAX, _lib.STAT_FMIN)
+
+
+_MOMENTS = reduction.MOMENTS
 
 
 @functools.lru_cache(maxsize=256)
@@ -251,86 +250,17 @@ FUSE_SWAP_MOMENTS = os.environ.get("BOLT_AMD_FUSE_SWAP_MOMENTS", "1") != "0"
 _FUSE_SWAP_MIN_BYTES = 256 << 20
 _FUSE_SWAP_STATE_DIV = 64
 
-_REDUCE_PLANS = {}  # (local shape, axes, stat, dtype, world) -> device reduction plan
-_MOMENT_PLANS = {}  # (local shape, axes, dtype, shape, world) -> device plan of stats() (one read, several moments)
+# A moment state held for some axes (the ``_kept`` dict of an array, keyed by the
+# sorted axes): the STAT_VAR ``state`` of ``nlaunch`` outputs over ``count``
+# values each, ``drop`` as reduction.Source's; ``serves_mean``: mean() is
+# finished from it too (a state the swap's transpose left), not only var / std.
+Kept = collections.namedtuple('Kept', ('state', 'count', 'nlaunch', 'drop', 'serves_mean'))
 
 # stats(): one StatCounter pass read for several moments (statcounter.py:30-48)
 Stats = collections.namedtuple('Stats', ('count', 'mean', 'var', 'std'))
-_STATS_FIELDS = ('mean', 'var', 'std')  # the order of bm_reduce_moments' outputs
+_STATS_FIELDS = reduction.STATS_FIELDS
 _STATS_NAMES = {'mean': 'mean', 'var': 'var', 'variance': 'var', 'std': 'std', 'stdev': 'std'}
 _STAT_AXES = {}  # (shape, split, axis as given) -> (validated axes, records after _align, record shape | None)
-
-
-def _moment_planes(be, dev, out_dtype, want, n, launch, host_ok):
-    """One buffer of a plane of ``n`` values per moment of ``want``, filled by
-    ``launch((mean, var, std) tensors, None where not asked for)``: page-locked
-    host memory when the kernels can store into it (``host_ok``: one rank), else
-    HBM.  -> (host ndarray (len(want), n), or a list of its rows, after one
-    stream synchronise, None) or (None, device buffer)."""
-    nb = n * out_dtype.itemsize
-    host = host_result(be, len(want) * nb, dev) if host_ok else None
-    if host is None and host_ok and nb <= HOST_RESULT_MAX < len(want) * nb:
-        # the planes together pass the zero-copy limit, each alone does not
-        # (C4's 8 MiB float64 planes): a page-locked buffer per plane, as the
-        # single statistics get -- a staged D2H of the planes cost 0.76 ms
-        # there, more than the saved read (profiles/stats_fused_ab.log)
-        hosts = [host_result(be, nb, dev) for _ in want]
-        if all(h is not None for h in hosts):
-            outs = [None, None, None]
-            for h, f in zip(hosts, want):
-                outs[_STATS_FIELDS.index(f)] = h
-            launch(tuple(outs))
-            first = finish_host_result(hosts[0], dev, out_dtype, (n,))
-            return [first] + [h.numpy().view(out_dtype) for h in hosts[1:]], None
-    buf = host if host is not None else _empty(len(want) * nb, dev)
-    outs = [None, None, None]
-    for j, f in enumerate(want):
-        outs[_STATS_FIELDS.index(f)] = buf[j * nb:(j + 1) * nb]
-    launch(tuple(outs))
-    if host is not None:
-        return finish_host_result(host, dev, out_dtype, (len(want), n)), None
-    return None, buf
-
-
-def _combine_moments(be, code, ocode, out_dtype, want, states, counts, nout, host_ok):
-    """STAT_VAR states of ``len(counts)`` parts -> _moment_planes' result."""
-    if hasattr(be, "reduce_combine_moments"):
-        return _moment_planes(be, states.device, out_dtype, want, nout,
-                              lambda outs: be.reduce_combine_moments(code, states, counts, nout, outs, ocode),
-                              host_ok)
-
-    def per_field(outs):
-        # an executor without the fused entry points (the CPU test executor):
-        # the same states merged once per moment; the mean's merge takes the
-        # one-plane STAT_MEAN layout (the mean planes, part-major)
-        om, ov, osd = outs
-        with np.errstate(all="ignore"):  # a numpy executor on pad columns' unwritten values (dropped later)
-            if om is not None:
-                means = states.view(len(counts), 2, nout * 8)[:, 0, :].contiguous().view(-1)
-                be.reduce_combine(_lib.STAT_MEAN, code, means, counts, nout, om, ocode)
-            if ov is not None:
-                be.reduce_combine(_lib.STAT_VAR, code, states, counts, nout, ov, ocode)
-            if osd is not None:
-                be.reduce_combine(_lib.STAT_STD, code, states, counts, nout, osd, ocode)
-    return _moment_planes(be, states.device, out_dtype, want, nout, per_field, host_ok)
-
-
-def _launch_moments(be, src, es, code, ocode, out_dtype, want, O, R, I, pitch, host_ok):
-    """The moments ``want`` of one read of ``src`` ([O][R][I] elements of ``es``
-    bytes, rows ``pitch`` elements apart when I == 1) -> _moment_planes' result."""
-    if hasattr(be, "reduce_moments"):
-        return _moment_planes(be, src.device, out_dtype, want, O * I,
-                              lambda outs: be.reduce_moments(src, code, O, R, I, pitch, outs, ocode), host_ok)
-    # an executor without the fused entry points: still one read, into a
-    # STAT_VAR state that every moment is finalised from
-    if pitch != R:
-        dense = _empty(O * R * es, src.device)
-        be.copy_strided(src, 0, dense, 0, [O, R], [pitch, 1], [R, 1], es)
-        src = dense
-    state = _empty(be.state_bytes(_lib.STAT_VAR, code, O * I), src.device)
-    with np.errstate(all="ignore"):  # pad columns' unwritten values, as in _combine_moments
-        be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
-    return _combine_moments(be, code, ocode, out_dtype, want, state, [R], O * I, host_ok)
 
 
 class BoltArrayMI355X(BoltArray):
@@ -575,36 +505,31 @@ class BoltArrayMI355X(BoltArray):
             else:
                 src, sstr = self._data, None
             be = backend_for(src.device)
+            R = new_shape[-1]
             if pp is not None:
                 P, rows, oshape, psstr, dstr = pp
-                pbuf = _empty(rows * P * es, src.device)
-                csstr = psstr if sstr is None else sstr
-                st = self._swap_state(be, src.device, new_shape, es, oshape, csstr, dstr, P)
-                if st is None:
-                    be.copy_strided(src, 0, pbuf, 0, oshape, csstr, dstr, es)
-                    return self._derive_padded(pbuf, P, new_shape, split)
-                fused = be.copy_strided(src, 0, pbuf, 0, oshape, csstr, dstr, es,
-                                        moments=(st[0], new_shape[-1], P, st[1], st[2]))
-                return self._derive_padded(pbuf, P, new_shape, split)._with_swap_state(st, fused)
-            dstr = _padded_strides(new_shape, new_shape[-1])
-            if sstr is None:
-                # bm_permute's own strides: the same kernels, through the entry that takes the state
-                cstr = _padded_strides(self._shape, self._shape[-1])
-                csstr = [cstr[p] for p in perm]
             else:
-                csstr = sstr
-            st = self._swap_state(be, src.device, new_shape, es, list(new_shape), csstr, dstr, new_shape[-1])
-            if sstr is None and st is None:
-                data = permute_sharded(self._ctx, be, src, self._shape, perm, es)
+                P, oshape, dstr = R, list(new_shape), _padded_strides(new_shape, R)
+                if sstr is None:
+                    # bm_permute's own strides: the same kernels, through the entry that takes the state
+                    cstr = _padded_strides(self._shape, self._shape[-1])
+                    psstr = [cstr[p] for p in perm]
+            csstr = psstr if sstr is None else sstr
+            st = self._swap_state(be, src.device, new_shape, es, oshape, csstr, dstr, P)
+            if pp is None and sstr is None and st is None:
+                # dense to dense and no state wanted: bm_permute's own launch
+                return self._derive(permute_sharded(self._ctx, be, src, self._shape, perm, es), new_shape, split)
+            # the one-GPU copy: padded or dense rows, with or without their state
+            n = rows * P if pp is not None else int(np.prod(new_shape, dtype=np.int64))
+            dst = _empty(n * es, src.device)
+            if st is None:
+                be.copy_strided(src, 0, dst, 0, oshape, csstr, dstr, es)
+                fused = False
             else:
-                n = int(np.prod(new_shape, dtype=np.int64))
-                data = _empty(n * es, src.device)
-                if st is None:
-                    be.copy_strided(src, 0, data, 0, list(new_shape), csstr, dstr, es)
-                else:
-                    fused = be.copy_strided(src, 0, data, 0, list(new_shape), csstr, dstr, es,
-                                            moments=(st[0], new_shape[-1], new_shape[-1], st[1], st[2]))
-                    return self._derive(data, new_shape, split)._with_swap_state(st, fused)
+                fused = be.copy_strided(src, 0, dst, 0, oshape, csstr, dstr, es, moments=(st[0], R, P, st[1], st[2]))
+            out = self._derive_padded(dst, P, new_shape, split) if pp is not None \
+                else self._derive(dst, new_shape, split)
+            return out._with_swap_state(st, fused)
         else:
             # across GPUs: the exchange's pack reads a padded source in place
             # and its unpack writes the result's rows at the same pitch rule
@@ -639,10 +564,10 @@ class BoltArrayMI355X(BoltArray):
         return code, rows, _empty(be.state_bytes(_lib.STAT_VAR, code, rows), dev)
 
     def _with_swap_state(self, st, fused):
-        """Remember the state a move left (``fused``) for the last axis; the
-        mark lets mean() be served from it too (see _reduced)."""
+        """Remember the state a move left (``fused``) for the last axis; it
+        serves mean() too (see _kept_for)."""
         if fused:
-            self.__dict__["_kept"] = {(len(self._shape) - 1,): (st[2], self._shape[-1], st[1], None, True)}
+            self.__dict__["_kept"] = {(len(self._shape) - 1,): Kept(st[2], self._shape[-1], st[1], None, True)}
         return self
 
     def _pitch_of(self, mv, es):
@@ -1187,148 +1112,64 @@ class BoltArrayMI355X(BoltArray):
     def _reduced(self, axis, stat):
         """Device reduction of ``axis`` -> host ndarray with the kept axes (ascending).
 
-        Returns (result ndarray, out dtype).  Layout per plan.reduce_layout;
-        if the reduced axes are not one block they are first permuted to the
-        front (what _align's swap does physically, array.py:85-115).
+        Returns (result ndarray, out dtype).  Plan, source layouts and the
+        finish are reduction.py's; what is kept and served is decided here.
         """
-        ctx = self._ctx
-        lshape = self._local_shape
-        pkey = (lshape, tuple(axis), stat, self._dtype, self._shape, ctx.world_size)
-        plan = _REDUCE_PLANS.get(pkey)
-        if plan is None:
-            axset = sorted(set(int(a) for a in axis))
-            kept = [i for i in range(self.ndim) if i not in axset]
-            out_shape = tuple(self._shape[i] for i in kept)
-            if stat in _KEEP_DTYPE:
-                out_dtype = self._dtype
-            elif stat in (_lib.STAT_LAND, _lib.STAT_LOR):
-                out_dtype = np.dtype(bool)
-            else:
-                out_dtype = stat_dtype(self._dtype, out_shape)
-            perm, O, R, I = reduce_layout(lshape, axset)
-            loc_out = tuple(lshape[i] for i in kept)
-            plan = (axset, kept, out_shape, out_dtype, dtype_code(self._dtype), dtype_code(out_dtype),
-                    perm, O, R, I, int(np.prod(lshape, dtype=np.int64)), loc_out,
-                    int(np.prod(loc_out, dtype=np.int64)))
-            if len(_REDUCE_PLANS) > 4096:
-                _REDUCE_PLANS.clear()
-            _REDUCE_PLANS[pkey] = plan
-        axset, kept, out_shape, out_dtype, code, ocode, perm, O, R, I, nloc, loc_out, nout = plan
-        held = self.__dict__.get("_kept")
-        if held and KEEP_MOMENTS and stat in (_lib.STAT_VAR, _lib.STAT_STD) and tuple(axset) in held:
-            return self._from_kept(held[tuple(axset)], stat, code, ocode, out_dtype, out_shape), out_dtype
-        if held and stat in _MOMENTS and len(held.get(tuple(axset), ())) > 4:
-            # a state left by the swap's transpose (_with_swap_state) serves the mean too
-            return self._from_kept(held[tuple(axset)], stat, code, ocode, out_dtype, out_shape), out_dtype
-        pbuf = self.__dict__.get("_pbuf")
-        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and ctx.world_size > 1 \
-                and 0 not in axset:
-            # last-axis statistic of a row-padded slab: every output is this
-            # rank's, read in place, then gathered like the dense path's
-            be = backend_for(pbuf.device)
-            out = _empty(nout * out_dtype.itemsize, pbuf.device)
-            if nout and nloc:
-                be.reduce_rows(stat, pbuf, code, O, R, self._pitch, out, ocode)
-            sizes = [int(np.prod((hi - lo,) + out_shape[1:], dtype=np.int64)) * out_dtype.itemsize
-                     for lo, hi in ctx.bounds(self._shape[0])]
-            return to_host(all_gather_bytes(ctx, out, sizes), out_dtype, out_shape), out_dtype
-        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and nloc and ctx.world_size == 1:
-            # last-axis statistic of a row-padded array: read the rows in place
-            be = backend_for(pbuf.device)
-            st = self._keep_state(be, pbuf.device, axset, stat, code, nout, nloc, False)
-            host = host_result(be, nout * out_dtype.itemsize, pbuf.device)
-            if host is not None:
-                self._keeping(axset, be.reduce_rows, (stat, pbuf, code, O, R, self._pitch, host, ocode), st, R, nout)
-                return finish_host_result(host, pbuf.device, out_dtype, out_shape), out_dtype
-            out = _empty(nout * out_dtype.itemsize, pbuf.device)
-            self._keeping(axset, be.reduce_rows, (stat, pbuf, code, O, R, self._pitch, out, ocode), st, R, nout)
-            return to_host(out, out_dtype, out_shape), out_dtype
-        if pbuf is not None and perm is None and I > 1 and I % lshape[-1] == 0 and nloc and ctx.world_size == 1:
-            # leading / middle axes of a row-padded array: the columns run over
-            # the padded rows as if the last axis were P long; every column is
-            # its own reduction, so the pad columns' (unwritten) values reach
-            # only their own outputs, which are dropped
-            be = backend_for(pbuf.device)
-            Rl, P = lshape[-1], self._pitch
-            Ip = I // Rl * P
-            nb = O * Ip * out_dtype.itemsize
-            # the kept state holds the pad columns' states too: dropped as here
-            st = self._keep_state(be, pbuf.device, axset, stat, code, O * Ip, O * R * Ip, True)
-            drop = (O, I // Rl, P, Rl)
-            host = host_result(be, nb, pbuf.device)
-            if host is not None:
-                self._keeping(axset, be.reduce, (stat, pbuf, code, O, R, Ip, host, ocode), st, R, O * Ip, drop)
-                full = finish_host_result(host, pbuf.device, out_dtype, (O, I // Rl, P))
-            else:
-                out = _empty(nb, pbuf.device)
-                self._keeping(axset, be.reduce, (stat, pbuf, code, O, R, Ip, out, ocode), st, R, O * Ip, drop)
-                full = to_host(out, out_dtype, (O, I // Rl, P))
-            return np.ascontiguousarray(full[:, :, :Rl]).reshape(out_shape), out_dtype
-        if pbuf is not None and perm is None and O == 1 and I == 1 and R == nloc and nloc \
-                and ctx.world_size == 1 and len(lshape) >= 2 and stat in _MOMENTS \
-                and self._dtype.kind == "f" and self._dtype.itemsize >= 4:
-            return self._padded_all_moments(pbuf, stat, code, out_dtype, out_shape), out_dtype
-        be = self._backend
-        dev = self._device
-        es = self._dtype.itemsize
-        if perm is not None:
-            # the reduced axes first (_align's swap): a padded array is read in place
-            tmp = _empty(nloc * es, dev)
-            if pbuf is not None:
-                pstr = _padded_strides(lshape, self._pitch)
-                pshape = [lshape[p] for p in perm]
-                be.copy_strided(pbuf, 0, tmp, 0, pshape, [pstr[p] for p in perm],
-                                _padded_strides(pshape, pshape[-1]), es)
-            elif nloc:
-                be.permute(self._data, lshape, perm, es, tmp)
-            src = tmp
-        else:
-            src = self._data
-
-        if ctx.world_size == 1 or 0 not in axset:
+        plan, out_dtype, ocode = reduction.plan_for(self, axis, stat)
+        axes, code = plan.axes, plan.code
+        entry = self._kept_for(axes, stat) if "_kept" in self.__dict__ else None
+        if entry is not None:
+            return self._from_kept(entry, stat, plan, out_dtype, ocode), out_dtype
+        src = reduction.source(self, plan, stat in _MOMENTS)
+        buf, O, R, I, pitch, nlaunch, drop, every = src
+        dev = buf.device
+        be = backend_for(dev)
+        if every:
+            mean, var = reduction.every_axis_moments(be, src, stat, code)
+            v = mean if stat == _lib.STAT_MEAN else var if stat == _lib.STAT_VAR else np.sqrt(var)
+            return np.asarray(v, dtype=np.float64).astype(out_dtype).reshape(plan.out_shape), out_dtype
+        single = plan.world == 1
+        if single or 0 not in axes:
             # every output lives on this rank (or this rank's slab of them)
-            host = host_result(be, nout * out_dtype.itemsize, dev) if ctx.world_size == 1 and nloc else None
-            # (a state kept after the permute above serves later calls without it)
-            st = self._keep_state(be, dev, axset, stat, code, nout, nloc, I > 1) if nout and nloc else None
-            if host is not None:
-                # the kernel stores the result into page-locked host memory
-                self._keeping(axset, be.reduce, (stat, src, code, O, R, I, host, ocode), st, R, nout)
-                return finish_host_result(host, dev, out_dtype, out_shape), out_dtype
-            out = _empty(nout * out_dtype.itemsize, dev)
-            if nout and nloc:
-                self._keeping(axset, be.reduce, (stat, src, code, O, R, I, out, ocode), st, R, nout)
-            if ctx.world_size > 1:
-                sizes = []
-                for lo, hi in ctx.bounds(self._shape[0]):
-                    sizes.append(int(np.prod((hi - lo,) + out_shape[1:], dtype=np.int64)) * out_dtype.itemsize)
-                out = all_gather_bytes(ctx, out, sizes)
-            return to_host(out, out_dtype, out_shape), out_dtype
+            run = nlaunch and plan.nloc
+            outs = reduction.outputs(be, dev, out_dtype, 1, nlaunch, single and run)
+            if run:
+                # the one reduce / reduce_rows call; with a state buffer the launch
+                # may keep its STAT_VAR state there, remembered for these axes (a
+                # state kept after source's permute serves later calls without it;
+                # a padded array's holds the pad columns' states too: dropped as
+                # the outputs)
+                st = self._keep_state(be, dev, axes, stat, code, nlaunch, O * R * I, I > 1)
+                fn, last = (be.reduce_rows, pitch) if pitch != R else (be.reduce, I)
+                if st is None:
+                    fn(stat, buf, code, O, R, last, outs[0][0], ocode)
+                elif fn(stat, buf, code, O, R, last, outs[0][0], ocode, state=st):
+                    self.__dict__.setdefault("_kept", {})[axes] = Kept(st, R, nlaunch, drop, False)
+            return reduction.finish(outs, dev, plan, out_dtype, 1, nlaunch, drop, None if single else self._ctx)[0], \
+                out_dtype
+        # the sharded axis is reduced: per-rank states, gathered and combined in rank order
+        if plan.nout == 0:  # e.g. mean(axis=0) of (4, 0, 3): nothing to merge
+            return np.empty(plan.out_shape, out_dtype), out_dtype
+        states, counts = reduction.sharded_states(self._ctx, be, dev, plan, stat, src)
+        outs = reduction.outputs(be, dev, out_dtype, 1, plan.nout, False)
+        be.reduce_combine(stat, code, states, counts, plan.nout, outs[0][0], ocode)
+        return reduction.finish(outs, dev, plan, out_dtype, 1, plan.nout)[0], out_dtype
 
-        # the sharded axis is reduced: per-rank states, gathered and combined
-        # in rank order (statcounter.py:67-99, deterministic here)
-        nout = int(np.prod(out_shape, dtype=np.int64))
-        if nout == 0:  # e.g. mean(axis=0) of (4, 0, 3): nothing to merge
-            return np.empty(out_shape, out_dtype), out_dtype
-        if ctx.world_size > _lib.MAX_COMBINE_PARTS:
-            raise NotImplementedError("reductions over the sharded axis merge at most %d ranks (got %d)"
-                                      % (_lib.MAX_COMBINE_PARTS, ctx.world_size))
-        sbytes = be.state_bytes(stat, code, nout)
-        state = _empty(sbytes, dev)
-        count = int(np.prod([lshape[i] for i in axset], dtype=np.int64))
-        if count:
-            be.reduce_state(stat, src, code, O, R, I, state)
-        else:
-            state.zero_()
-        counts = []
-        for lo, hi in ctx.bounds(self._shape[0]):
-            c = (hi - lo) * int(np.prod([self._shape[i] for i in axset if i != 0], dtype=np.int64))
-            counts.append(c)
-        states = all_gather_bytes(ctx, state, [sbytes] * ctx.world_size)
-        out = _empty(nout * out_dtype.itemsize, dev)
-        be.reduce_combine(stat, code, states, counts, nout, out, ocode)
-        return to_host(out, out_dtype, out_shape), out_dtype
+    def _kept_for(self, axes, stat):
+        """The kept state that serves ``stat`` over ``axes`` without a read of
+        the array, or None.  The rule: var / std are served from any kept state
+        when KEEP_MOMENTS is on (a later mean() reads again: its bits come from
+        other arithmetic than the state's mean); mean, var and std are all
+        served from a state that serves the mean -- one the swap's transpose
+        left (_with_swap_state) -- whatever KEEP_MOMENTS says."""
+        held = self.__dict__.get("_kept")
+        entry = held.get(axes) if held else None
+        if entry is not None and stat in _MOMENTS \
+                and (entry.serves_mean or (KEEP_MOMENTS and stat != _lib.STAT_MEAN)):
+            return entry
+        return None
 
-    def _keep_state(self, be, dev, axset, stat, code, nlaunch, nread, cols):
+    def _keep_state(self, be, dev, axes, stat, code, nlaunch, nread, cols):
         """The buffer a mean / var / std launch of ``nlaunch`` outputs over
         ``nread`` elements stores its STAT_VAR state into, or None where none
         is kept (the rule is at KEEP_MOMENTS) or these axes' is held already.
@@ -1339,195 +1180,58 @@ class BoltArrayMI355X(BoltArray):
         if cols and not _KEEP_COLS:
             return None
         held = self.__dict__.get("_kept")
-        if held and tuple(axset) in held:
+        if held and axes in held:
             return None
         nbytes = nread * self._dtype.itemsize
         if nbytes <= _KEEP_MIN_BYTES or 16 * nlaunch > nbytes // _KEEP_STATE_DIV:
             return None
         return _empty(be.state_bytes(_lib.STAT_VAR, code, nlaunch), dev)
 
-    def _keeping(self, axset, launch, args, state, count, nlaunch, drop=None):
-        """The branch's one reduce / reduce_rows call; with ``state`` the
-        launch may keep its STAT_VAR state there, remembered for these axes."""
-        if state is None:
-            launch(*args)
-        elif launch(*args, state=state):
-            self.__dict__.setdefault("_kept", {})[tuple(axset)] = (state, count, nlaunch, drop)
-
-    def _from_kept(self, entry, stat, code, ocode, out_dtype, out_shape):
-        """var / std finished from a kept state: one reduce_combine of one part
-        into the host result of the branch that kept it, no read of the array."""
-        state, count, nlaunch, drop = entry[:4]
-        dev = state.device
+    def _from_kept(self, entry, stat, plan, out_dtype, ocode):
+        """A statistic finished from a kept state: one reduce_combine of one part
+        into the host result of the launch that kept it, no read of the array."""
+        dev = entry.state.device
         be = backend_for(dev)
-        shape = out_shape if drop is None else drop[:3]
-        host = host_result(be, nlaunch * out_dtype.itemsize, dev)
-        with np.errstate(all="ignore"):  # pad columns' unwritten values, as in _combine_moments
-            if host is not None:
-                be.reduce_combine(stat, code, state, [count], nlaunch, host, ocode)
-                full = finish_host_result(host, dev, out_dtype, shape)
-            else:
-                out = _empty(nlaunch * out_dtype.itemsize, dev)
-                be.reduce_combine(stat, code, state, [count], nlaunch, out, ocode)
-                full = to_host(out, out_dtype, shape)
-        if drop is None:
-            return full
-        return np.ascontiguousarray(full[:, :, :drop[3]]).reshape(out_shape)
-
-    def _padded_all_moments(self, pbuf, stat, code, out_dtype, out_shape):
-        """mean / var / std over every axis of a row-padded float array, read in
-        place: the padded rows are one (rows, pitch) matrix whose columns get a
-        float64 mean (and M2 for var / std) state each over all rows
-        (bm_reduce_state, the pad columns' states dropped); the row-length states, all of the same count,
-        merge on the host -- the StatCounter merge of statcounter.py:67-99 for
-        equal counts: mean = mean of the column means, M2 = sum of the column
-        M2 + rows * sum of squared deviations of the column means.  No dense
-        copy of the array is made; the summation order differs from the dense
-        layout's (results within 1e-12 relative in float64, rounded once)."""
-        be = backend_for(pbuf.device)
-        Rl, P = self._local_shape[-1], self._pitch
-        nrows = int(np.prod(self._local_shape[:-1], dtype=np.int64))
-        state = _empty(be.state_bytes(stat, code, P), pbuf.device)
-        be.reduce_state(stat, pbuf, code, 1, nrows, P, state)
-        planes = to_host(state, np.float64, (-1, P))   # mean [, M2] (bm_reduce_state)
-        means = planes[0, :Rl]
-        mean = means.mean()
-        if stat == _lib.STAT_MEAN:
-            v = mean
-        else:
-            v = (planes[1, :Rl].sum() + nrows * np.square(means - mean).sum()) / (nrows * Rl)
-            if stat == _lib.STAT_STD:
-                v = np.sqrt(v)
-        return np.asarray(v, dtype=np.float64).astype(out_dtype).reshape(out_shape)
+        outs = reduction.outputs(be, dev, out_dtype, 1, entry.nlaunch, True)
+        with np.errstate(all="ignore"):  # pad columns' unwritten values, as in reduction.combine_moments
+            be.reduce_combine(stat, plan.code, entry.state, [entry.count], entry.nlaunch, outs[0][0], ocode)
+            return reduction.finish(outs, dev, plan, out_dtype, 1, entry.nlaunch, entry.drop)[0]
 
     def _reduced_moments(self, axis, want):
         """_reduced for several moments of one read: ``want`` is a subset of
         ('mean', 'var', 'std') in that order -> {field: host ndarray with the
-        kept axes (ascending)}.  The layouts are _reduced's, branch for branch;
-        the data is read by one STAT_VAR launch sequence (bm_reduce_moments),
-        so var and std carry the bits of their own methods."""
-        ctx = self._ctx
-        lshape = self._local_shape
-        pkey = (lshape, tuple(axis), self._dtype, self._shape, ctx.world_size)
-        plan = _MOMENT_PLANS.get(pkey)
-        if plan is None:
-            axset = sorted(set(int(a) for a in axis))
-            kept = [i for i in range(self.ndim) if i not in axset]
-            out_shape = tuple(self._shape[i] for i in kept)
-            out_dtype = stat_dtype(self._dtype, out_shape)
-            perm, O, R, I = reduce_layout(lshape, axset)
-            loc_out = tuple(lshape[i] for i in kept)
-            plan = (axset, out_shape, out_dtype, dtype_code(self._dtype), dtype_code(out_dtype),
-                    perm, O, R, I, int(np.prod(lshape, dtype=np.int64)), int(np.prod(loc_out, dtype=np.int64)))
-            if len(_MOMENT_PLANS) > 4096:
-                _MOMENT_PLANS.clear()
-            _MOMENT_PLANS[pkey] = plan
-        axset, out_shape, out_dtype, code, ocode, perm, O, R, I, nloc, nout = plan
-        k = len(want)
-        es = self._dtype.itemsize
-        pbuf = self.__dict__.get("_pbuf")
-        single = ctx.world_size == 1
-
-        def fields(planes):
-            return dict((f, planes[j].reshape(out_shape)) for j, f in enumerate(want))
-
-        def gathered(buf):
-            # per-rank (k, this rank's outputs) planes -> (k, every output)
-            isz = out_dtype.itemsize
-            sizes = [k * int(np.prod((hi - lo,) + out_shape[1:], dtype=np.int64)) * isz
-                     for lo, hi in ctx.bounds(self._shape[0])]
-            flat = to_host(all_gather_bytes(ctx, buf, sizes), out_dtype, (-1,))
-            parts, off = [], 0
-            for s in sizes:
-                n = s // isz
-                parts.append(flat[off:off + n].reshape(k, n // k))
-                off += n
-            return np.concatenate(parts, axis=1)
-
-        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and not single and 0 not in axset:
-            # last-axis statistics of a row-padded slab, read in place, then gathered
-            be = backend_for(pbuf.device)
-            if nout and nloc:
-                _, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, 1, self._pitch, False)
-            else:
-                buf = _empty(0, pbuf.device)
-            return fields(gathered(buf))
-        if pbuf is not None and perm is None and I == 1 and R == lshape[-1] and nloc and single:
-            # last-axis statistics of a row-padded array: the rows read in place
-            be = backend_for(pbuf.device)
-            host, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, 1, self._pitch, True)
-            return fields(host if host is not None else to_host(buf, out_dtype, (k, nout)))
-        if pbuf is not None and perm is None and I > 1 and I % lshape[-1] == 0 and nloc and single:
-            # leading / middle axes of a row-padded array: columns over the
-            # padded rows, the pad columns' outputs dropped (see _reduced)
-            be = backend_for(pbuf.device)
-            Rl, P = lshape[-1], self._pitch
-            Ip = I // Rl * P
-            host, buf = _launch_moments(be, pbuf, es, code, ocode, out_dtype, want, O, R, Ip, R, True)
-            full = host if host is not None else to_host(buf, out_dtype, (k, O * Ip))
-            return dict((f, np.ascontiguousarray(full[j].reshape(O, I // Rl, P)[:, :, :Rl]).reshape(out_shape))
-                        for j, f in enumerate(want))
-        if pbuf is not None and perm is None and O == 1 and I == 1 and R == nloc and nloc \
-                and single and len(lshape) >= 2 and self._dtype.kind == "f" and self._dtype.itemsize >= 4:
-            # every axis of a row-padded float array: the one column state of
-            # _padded_all_moments holds the mean and M2 of every moment
-            be = backend_for(pbuf.device)
-            Rl, P = lshape[-1], self._pitch
-            nrows = nloc // Rl
-            state = _empty(be.state_bytes(_lib.STAT_VAR, code, P), pbuf.device)
-            be.reduce_state(_lib.STAT_VAR, pbuf, code, 1, nrows, P, state)
-            planes = to_host(state, np.float64, (-1, P))
-            means = planes[0, :Rl]
-            mean = means.mean()
-            var = (planes[1, :Rl].sum() + nrows * np.square(means - mean).sum()) / (nrows * Rl)
+        kept axes (ascending)}.  The data is read by one STAT_VAR launch
+        sequence (bm_reduce_moments), so var and std carry the bits of their
+        own methods."""
+        plan, out_dtype, ocode = reduction.plan_for(self, axis, _lib.STAT_VAR)
+        src = reduction.source(self, plan)
+        nlaunch, drop, every = src[5:]
+        dev = src.buf.device
+        be = backend_for(dev)
+        code, k = plan.code, len(want)
+        single = plan.world == 1
+        if every:
+            mean, var = reduction.every_axis_moments(be, src, _lib.STAT_VAR, code)
             vals = {'mean': mean, 'var': var, 'std': np.sqrt(var)}
-            return dict((f, np.asarray(vals[f], dtype=np.float64).astype(out_dtype).reshape(out_shape))
+            return dict((f, np.asarray(vals[f], dtype=np.float64).astype(out_dtype).reshape(plan.out_shape))
                         for f in want)
-        be = self._backend
-        dev = self._device
-        if perm is not None:
-            # the reduced axes first (_align's swap), once for every moment
-            tmp = _empty(nloc * es, dev)
-            if pbuf is not None:
-                pstr = _padded_strides(lshape, self._pitch)
-                pshape = [lshape[p] for p in perm]
-                be.copy_strided(pbuf, 0, tmp, 0, pshape, [pstr[p] for p in perm],
-                                _padded_strides(pshape, pshape[-1]), es)
-            elif nloc:
-                be.permute(self._data, lshape, perm, es, tmp)
-            src = tmp
-        else:
-            src = self._data
-
-        if single or 0 not in axset:
+        if single or 0 not in plan.axes:
             # every output lives on this rank (or this rank's slab of them)
-            if nout and nloc:
-                host, buf = _launch_moments(be, src, es, code, ocode, out_dtype, want, O, R, I, R, single)
-            else:
-                host, buf = None, _empty(0, dev)
-            if not single:
-                return fields(gathered(buf))
-            return fields(host if host is not None else to_host(buf, out_dtype, (k, nout)))
-
-        # the sharded axis is reduced: one STAT_VAR state per rank, gathered
-        # once and merged in rank order into every moment
-        nout = int(np.prod(out_shape, dtype=np.int64))
-        if nout == 0:
-            return dict((f, np.empty(out_shape, out_dtype)) for f in want)
-        if ctx.world_size > _lib.MAX_COMBINE_PARTS:
-            raise NotImplementedError("reductions over the sharded axis merge at most %d ranks (got %d)"
-                                      % (_lib.MAX_COMBINE_PARTS, ctx.world_size))
-        sbytes = be.state_bytes(_lib.STAT_VAR, code, nout)
-        state = _empty(sbytes, dev)
-        if int(np.prod([lshape[i] for i in axset], dtype=np.int64)):
-            be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
+            run = nlaunch and plan.nloc
+            outs = reduction.outputs(be, dev, out_dtype, k, nlaunch, single and run)
+            if run:
+                reduction.launch_moments(be, src, self._dtype.itemsize, code, ocode, want, outs[0])
+            res = reduction.finish(outs, dev, plan, out_dtype, k, nlaunch, drop, None if single else self._ctx)
+        elif plan.nout == 0:
+            return dict((f, np.empty(plan.out_shape, out_dtype)) for f in want)
         else:
-            state.zero_()
-        counts = [(hi - lo) * int(np.prod([self._shape[i] for i in axset if i != 0], dtype=np.int64))
-                  for lo, hi in ctx.bounds(self._shape[0])]
-        states = all_gather_bytes(ctx, state, [sbytes] * ctx.world_size)
-        _, buf = _combine_moments(be, code, ocode, out_dtype, want, states, counts, nout, False)
-        return fields(to_host(buf, out_dtype, (k, nout)))
+            # the sharded axis is reduced: one STAT_VAR state per rank, gathered
+            # once and merged in rank order into every moment
+            states, counts = reduction.sharded_states(self._ctx, be, dev, plan, _lib.STAT_VAR, src)
+            outs = reduction.outputs(be, dev, out_dtype, k, plan.nout, False)
+            reduction.combine_moments(be, code, ocode, want, states, counts, plan.nout, outs[0])
+            res = reduction.finish(outs, dev, plan, out_dtype, k, plan.nout)
+        return dict(zip(want, res))
 
     def stats(self, axis=None, keepdims=False, names=_STATS_FIELDS):
         """Several moments over ``axis`` from one read of the array: the
@@ -1602,24 +1306,20 @@ class BoltArrayMI355X(BoltArray):
         Moment states (KEEP_MOMENTS) are neither used nor left."""
         ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
         inshape(self.shape, ax)
-        ctx = self._ctx
-        lshape = self._local_shape
-        out_dtype = stat_dtype(self._dtype, (1,))
-        code, ocode = dtype_code(self._dtype), dtype_code(out_dtype)
+        plan, out_dtype, ocode = reduction.plan_for(self, ax, reduction.STANDARDIZE)
+        code = plan.code
         dev = self._device
         if self.size == 0:
             return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
         be = backend_for(dev)
-        axset = sorted(set(int(a) for a in ax))
-        perm, O, R, I = reduce_layout(lshape, axset)
-        nloc = int(np.prod(lshape, dtype=np.int64))
+        perm, O, R, I, nloc = plan.perm, plan.O, plan.R, plan.I, plan.nloc
         es, oes = self._dtype.itemsize, out_dtype.itemsize
         d = self.__dict__
         pbuf, P = d.get("_pbuf"), d.get("_pitch")
         # every reduced record lies whole on this rank
-        local = ctx.world_size == 1 or 0 not in axset
+        local = plan.world == 1 or 0 not in plan.axes
         # the reduced axis is the last one: rows, a pitch apart
-        rows_last = perm is None and I == 1 and local and (pbuf is None or R == lshape[-1])
+        rows_last = perm is None and I == 1 and local and (pbuf is None or R == plan.lshape[-1])
 
         if rows_last and nloc and hasattr(be, "standardize_rows"):
             keep_pad = pbuf is not None and oes == es
@@ -1633,55 +1333,29 @@ class BoltArrayMI355X(BoltArray):
                 new.__dict__["_dtype"] = out_dtype
                 return new
 
-        pitch = R
-        if perm is not None:
-            # the reduced axes first (_align's swap): a padded array is read in place
-            src = _empty(nloc * es, dev)
-            pshape = [lshape[p] for p in perm]
-            if pbuf is not None and nloc:
-                pstr = _padded_strides(lshape, P)
-                be.copy_strided(pbuf, 0, src, 0, pshape, [pstr[p] for p in perm],
-                                _padded_strides(pshape, pshape[-1]), es)
-            elif nloc:
-                be.permute(self._data, lshape, perm, es, src)
-        elif pbuf is not None and rows_last:
-            src, pitch = pbuf, P
-        elif pbuf is not None:
-            src = _empty(nloc * es, dev)
-            if nloc:
-                be.copy_strided(pbuf, 0, src, 0, [nloc // lshape[-1], lshape[-1]], [P, 1], [lshape[-1], 1], es)
-        else:
-            src = self._data
-
+        # a rank with an empty slab launches nothing, so it needs no source
+        src = reduction.source(self, plan, compact=True) if nloc else None
         want = ('mean', 'std') if scale else ('mean',)
         f64 = np.dtype(np.float64)
         fcode = dtype_code(f64)
-        planes = None
+        planes = None   # the float64 mean [, std] planes in HBM
         if local:
             nplane = O * I
             if nloc:
-                _, planes = _launch_moments(be, src, es, code, fcode, f64, want, O, R, I, pitch, False)
+                tensors, _, planes = reduction.outputs(be, dev, f64, len(want), nplane, False)
+                reduction.launch_moments(be, src, es, code, fcode, want, tensors)
         else:
             # the sharded axis is reduced: one STAT_VAR state per rank, gathered
             # and merged in rank order; every rank takes part, its launches only
             # where its slab has elements
-            nplane = int(np.prod([self._shape[i] for i in range(self.ndim) if i not in axset], dtype=np.int64))
-            if ctx.world_size > _lib.MAX_COMBINE_PARTS:
-                raise NotImplementedError("reductions over the sharded axis merge at most %d ranks (got %d)"
-                                          % (_lib.MAX_COMBINE_PARTS, ctx.world_size))
-            sbytes = be.state_bytes(_lib.STAT_VAR, code, nplane)
-            state = _empty(sbytes, dev)
-            if nloc:
-                be.reduce_state(_lib.STAT_VAR, src, code, O, R, I, state)
-            else:
-                state.zero_()
-            counts = [(hi - lo) * int(np.prod([self._shape[i] for i in axset if i != 0], dtype=np.int64))
-                      for lo, hi in ctx.bounds(self._shape[0])]
-            states = all_gather_bytes(ctx, state, [sbytes] * ctx.world_size)
-            _, planes = _combine_moments(be, code, fcode, f64, want, states, counts, nplane, False)
+            nplane = plan.nout
+            states, counts = reduction.sharded_states(self._ctx, be, dev, plan, _lib.STAT_VAR, src)
+            tensors, _, planes = reduction.outputs(be, dev, f64, len(want), nplane, False)
+            reduction.combine_moments(be, code, fcode, want, states, counts, nplane, tensors)
 
         dst = _empty(nloc * oes, dev)
         if nloc:
+            src, pitch = src.buf, src.pitch
             mean = planes[:nplane * 8]
             std = planes[nplane * 8:2 * nplane * 8] if scale else None
             if hasattr(be, "standardize_apply"):
@@ -1702,7 +1376,7 @@ class BoltArrayMI355X(BoltArray):
                 dst = F.as_bytes(y.to(F.torch_dtype(out_dtype)).contiguous())
             if perm is not None:
                 back = _empty(nloc * oes, dev)
-                be.permute(dst, pshape, [int(i) for i in np.argsort(perm)], oes, back)
+                be.permute(dst, [plan.lshape[p] for p in perm], [int(i) for i in np.argsort(perm)], oes, back)
                 dst = back
         return self._like(dst, self._shape, self._split, dtype=out_dtype)
 

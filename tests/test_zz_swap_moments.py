@@ -75,7 +75,7 @@ def _truth(rows, name):
 
 def _fused_state(arr):
     e = (arr.__dict__.get("_kept") or {}).get((arr.ndim - 1,))
-    return e if e is not None and len(e) > 4 else None
+    return e if e is not None and e.serves_mean else None
 
 
 # (dtype, shape, padded rows expected, state-size divisor)

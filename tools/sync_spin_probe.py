@@ -15,7 +15,7 @@ import torch
 import bench
 import bolt_amd as bolt
 from bolt_amd import MI355XContext
-from bolt_amd.mi355x import array as barray, transfer
+from bolt_amd.mi355x import reduction as barray, transfer
 
 dev = torch.device("cuda", 0)
 ctx = MI355XContext(device=dev)
