@@ -214,10 +214,10 @@ struct NoMom {};
 // half ends with the same bits.
 __device__ __forceinline__ double pair_fold16(double a, double b, int lane) {
   const bool hi = lane & 8;
-  double v = (hi ? b : a) + dpp_mov<0x140>(hi ? a : b);
-  v += dpp_mov<0x141>(v);
-  v += dpp_mov<0x4E>(v);
-  v += dpp_mov<0xB1>(v);
+  double v = (hi ? b : a) + dpp_mov_all<0x140>(hi ? a : b);
+  v += dpp_mov_all<0x141>(v);
+  v += dpp_mov_all<0x4E>(v);
+  v += dpp_mov_all<0xB1>(v);
   return v;
 }
 
@@ -250,7 +250,6 @@ __global__ void __launch_bounds__(kThreads)
                          3 * TA <= kThreads),
                 "moments: vectorised unfused tiles of float / double only");
   __shared__ double mst[MOM ? (2 * NSEG + 1) * TA : 1];  // S1[TA][NSEG], S2[TA][NSEG], K[TA]
-  double p1 = 0.0, p2 = 0.0, pK = 0.0;  // the even row of a pair
 
   for (uint64_t t = blockIdx.x; t < d.ntiles; t += gridDim.x) {
     // consecutive blocks walk dim b (the destination-contiguous one): their
@@ -299,18 +298,15 @@ __global__ void __launch_bounds__(kThreads)
     T *q = dst + b0;
     if constexpr (!MOM) q += dof;
     const bool fullB = (b0 + ib + VB <= d.Lb);
+    if constexpr (!MOM) {
 #pragma unroll
-    for (int it = 0; it < NS; ++it) {
-      const int ra = uy + it * RPB;
-      // (moments: every lane runs the fold, also those of rows past La)
-      if (MOM || a0 + ra < d.La) {
-        T w[VB];
+      for (int it = 0; it < NS; ++it) {
+        const int ra = uy + it * RPB;
+        if (a0 + ra < d.La) {
+          T w[VB];
 #pragma unroll
-        for (int k = 0; k < VB; ++k) w[k] = tile[ib + k][ra];
-        if (!MOM || a0 + ra < d.La) {
-          T *p = q + ib;
-          if constexpr (MOM) p += (dof + (a0 + ra) * d.da) * mo.pitch;
-          else p += arow<FUSED>(d, a0 + ra);
+          for (int k = 0; k < VB; ++k) w[k] = tile[ib + k][ra];
+          T *p = q + ib + arow<FUSED>(d, a0 + ra);
           if (fullB) {
             vstore_nt<T, VB>(p, w);
           } else {
@@ -319,33 +315,78 @@ __global__ void __launch_bounds__(kThreads)
               if (b0 + ib + k < d.Lb) p[k] = w[k];
           }
         }
-        if constexpr (MOM) {
-          const double K0 = (double)__builtin_bit_cast(F, tile[0][ra]);
-          const double K = K0 - K0 == 0.0 ? K0 : 0.0;  // finite, else 0
-          double s1 = 0.0, s2 = 0.0;
+      }
+    } else {
+      // the tile's live rows and columns, as 32-bit counts: a lane tests its
+      // own uy / ib against a scalar per row / column
+      const int na = (int)min((int64_t)TA, d.La - a0), nb = (int)min((int64_t)TB, d.Lb - b0);
+      // A tile wholly inside La x Lb takes a path without any mask, its rows
+      // scheduled as one block -- in the kernels whose LDS tile alone holds a
+      // CU to two blocks (f32 64x256, f64 32x256: what every large swap
+      // picks).  There registers do not bound the occupancy; the smaller
+      // tiles' kernels would pay for the second path with 2-8 VGPRs, f64
+      // 32x64 with a wave per SIMD, so they keep the masked path alone.
+      constexpr bool UNMASKED = sizeof(tile) > (48 << 10);
+      // One tile row: its store to p, and this lane's sums of its VB values
+      // around the row's pivot.  FULL: no row and no value is masked.  Every
+      // lane runs it, also those of rows past La.
+      const auto row_sums = [&](auto full, int it, T *p, double &s1, double &s2, double &K) {
+        constexpr bool FULL = decltype(full)::value;
+        const int ra = uy + it * RPB;
+        T w[VB];
 #pragma unroll
-          for (int k = 0; k < VB; ++k) {
-            const double y = b0 + ib + k < d.Lb ? (double)__builtin_bit_cast(F, w[k]) - K : 0.0;
-            s1 += y;
-            s2 = fma(y, y, s2);
-          }
-          if ((it & 1) == 0) {
-            p1 = s1;
-            p2 = s2;
-            pK = K;
+        for (int k = 0; k < VB; ++k) w[k] = tile[ib + k][ra];
+        if (FULL || uy < na - it * RPB) {
+          if (FULL || ib <= nb - VB) {
+            vstore_nt<T, VB>(p, w);
           } else {
-            const int lane = threadIdx.x & 63;
-            s1 = pair_fold16(p1, s1, lane);
-            s2 = pair_fold16(p2, s2, lane);
-            if ((lane & 7) == 0) {  // lane 0 of a segment: the even row, lane 8: the odd one
-              const int rr = (lane & 8) ? ra : ra - RPB, seg = ux / 16;
-              mst[rr * NSEG + seg] = s1;
-              mst[(TA + rr) * NSEG + seg] = s2;
-              if (seg == 0) mst[2 * TA * NSEG + rr] = (lane & 8) ? K : pK;
-            }
+#pragma unroll
+            for (int k = 0; k < VB; ++k)
+              if (ib < nb - k) p[k] = w[k];
           }
         }
-      }
+        // the pivot is chosen on the F word, then widened once: finite, else 0
+        const F k0 = __builtin_bit_cast(F, tile[0][ra]);
+        K = (double)(__builtin_isfinite(k0) ? k0 : F(0));
+        s1 = 0.0;
+        s2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < VB; ++k) {
+          const double y = (FULL || ib < nb - k) ? (double)__builtin_bit_cast(F, w[k]) - K : 0.0;
+          s1 += y;
+          s2 = fma(y, y, s2);
+        }
+      };
+      // the rows go in pairs (pair_fold16): both rows' sums are plain values
+      // (a row's address is the tile's first plus a block-uniform step, not
+      // 64-bit products of its own)
+      const auto row_pairs = [&](auto full) {
+        const int lane = threadIdx.x & 63;
+        T *const p0 = q + ib + (dof + (a0 + uy) * d.da) * mo.pitch;
+        const int64_t pstep = (int64_t)RPB * d.da * mo.pitch;
+#pragma unroll
+        for (int it = 0; it < NS; it += 2) {
+          const int ra = uy + it * RPB;
+          double e1, e2, eK, o1, o2, oK;
+          row_sums(full, it, p0 + it * pstep, e1, e2, eK);
+          row_sums(full, it + 1, p0 + (it + 1) * pstep, o1, o2, oK);
+          const double K = (lane & 8) ? oK : eK;  // before the folds: one pivot to hold, not two
+          const double s1 = pair_fold16(e1, o1, lane);
+          const double s2 = pair_fold16(e2, o2, lane);
+          if ((lane & 7) == 0) {  // lane 0 of a segment: the even row, lane 8: the odd one
+            const int rr = (lane & 8) ? ra + RPB : ra, seg = ux / 16;
+            mst[rr * NSEG + seg] = s1;
+            mst[(TA + rr) * NSEG + seg] = s2;
+            if (seg == 0) mst[2 * TA * NSEG + rr] = K;
+          }
+        }
+      };
+      // uniform over the block: a scalar branch, taken by every tile but the
+      // ragged ones at the end of dim b and of dim a; the sign of the 64-bit
+      // slack is tested on its high word, which stays in the scalar unit
+      const int64_t slack = (d.Lb - b0 - TB) | (d.La - a0 - TA);
+      if (UNMASKED && (int32_t)((uint64_t)slack >> 32) >= 0) row_pairs(std::true_type{});
+      else row_pairs(std::false_type{});
     }
     __syncthreads();
     if constexpr (MOM) {

@@ -350,10 +350,18 @@ struct Sink {
   double *k0, *k1;  // bm_reduce_keep: the BM_STAT_VAR state (absolute mean, M2) next to `out` (NULL: not kept)
 };
 
+// M2 as it leaves a kernel: not below 0 (rounding of S2 - S1^2 / n), and NaN
+// where the mean is not finite -- a NaN or an infinity among the values, for
+// which numpy's var / std are NaN.  (The sums of such a row give a NaN M2,
+// which a plain ``m2 > 0 ? m2 : 0`` turned into 0.)
+__device__ __forceinline__ double m2_out(double m2, double mean) {
+  return mean - mean == 0.0 ? (m2 > 0.0 ? m2 : 0.0) : __builtin_nan("");
+}
+
 // the kept copy of the var / std state of output idx: bm_reduce_state's values
 __device__ __forceinline__ void emit_kept(const Sink &sk, int64_t idx, double mean_y, double m2, double P) {
   sk.k0[idx] = P + mean_y;
-  sk.k1[idx] = m2 > 0.0 ? m2 : 0.0;
+  sk.k1[idx] = m2_out(m2, P + mean_y);
 }
 
 // var / std output of one (output, chunk): the Welford state is kept around
@@ -365,7 +373,7 @@ __device__ __forceinline__ void emit_kept(const Sink &sk, int64_t idx, double me
 // partials (chunk 0 records P), absolute for bm_reduce_state.
 __device__ __forceinline__ void emit_mom(const Sink &sk, int64_t idx, int64_t e, int64_t c, double n,
                                          double mean_y, double m2, double P) {
-  m2 = m2 > 0.0 ? m2 : 0.0;
+  m2 = m2_out(m2, P + mean_y);
   if (sk.k0) emit_kept(sk, idx, mean_y, m2, P);
   if (sk.final_out == kFinalMoments) {
     if (sk.om) store_out(sk.om, idx, n > 0.0 ? P + mean_y : 0.0, sk.out_dtype);
@@ -1579,7 +1587,7 @@ __global__ void __launch_bounds__(kThreads)
       m = s;
     }
     state[e] = m;
-    state[nrows + e] = q > 0.0 ? q : 0.0;
+    state[nrows + e] = m2_out(q, m);
   }
 }
 

@@ -22,6 +22,17 @@ template <int CTRL, typename V> __device__ __forceinline__ V dpp_mov(V v) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
   return __builtin_bit_cast(V, ((uint64_t)hi << 32) | lo);
 }
+// dpp_mov where all 64 lanes are active and CTRL gives every lane a source lane
+// (the mirrors and quad_perms): no lane keeps an old value, so none is set up
+// -- dpp_mov's zero costs a v_mov per 32-bit half in front of each move.
+template <int CTRL, typename V> __device__ __forceinline__ V dpp_mov_all(V v) {
+  static_assert(sizeof(V) == 8, "64-bit lane values");
+  static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "a source lane for every lane");
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, true);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
+  return __builtin_bit_cast(V, ((uint64_t)hi << 32) | lo);
+}
 // Lane 63 receives op over all 64 lanes, combined in lane order: every step
 // combines (lower lanes, upper lanes), so the result equals a left fold over
 // lanes 0..63 for any associative op (first NaN / first of equal values wins,

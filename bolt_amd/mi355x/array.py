@@ -250,11 +250,33 @@ FUSE_SWAP_MOMENTS = os.environ.get("BOLT_AMD_FUSE_SWAP_MOMENTS", "1") != "0"
 _FUSE_SWAP_MIN_BYTES = 256 << 20
 _FUSE_SWAP_STATE_DIV = 64
 
+# mean() and std() of a state the swap left are the pair of every z-score, and
+# the host is still ahead of the GPU when the first of them is called (the swap
+# is asynchronous).  So the first mean() finished from such a state also
+# queues std's finish right behind its own -- into a page-locked plane of its
+# own, with an event of its own -- and waits for the event behind its own
+# launch, not for the stream; the std() that follows waits for std's event and
+# returns the plane: no launch and no stream synchronise, where the GPU
+# otherwise idles ~0.033 ms while the host returns mean, calls std and
+# launches.  Symmetric: std() first queues mean's finish.  var() queues
+# nothing (a var / std pair is not a pattern the reference's users show).  One
+# plane per state, queued by the first of the two calls and handed out once;
+# any later call goes the plain way.  Only where the result plane takes the
+# page-locked result path.  unpersist() drops the queued plane.  The cost where
+# the other statistic never follows: one 0.021 ms kernel and 1 MiB of
+# page-locked memory (C2) per first mean(), queued behind the result the
+# caller is waiting for.  FINISH_AHEAD = False (BOLT_AMD_FINISH_AHEAD=0): off.
+FINISH_AHEAD = os.environ.get("BOLT_AMD_FINISH_AHEAD", "1") != "0"
+_AHEAD_OF = {_lib.STAT_MEAN: _lib.STAT_STD, _lib.STAT_STD: _lib.STAT_MEAN}
+
 # A moment state held for some axes (the ``_kept`` dict of an array, keyed by the
 # sorted axes): the STAT_VAR ``state`` of ``nlaunch`` outputs over ``count``
 # values each, ``drop`` as reduction.Source's; ``serves_mean``: mean() is
-# finished from it too (a state the swap's transpose left), not only var / std.
-Kept = collections.namedtuple('Kept', ('state', 'count', 'nlaunch', 'drop', 'serves_mean'))
+# finished from it too (a state the swap's transpose left), not only var / std;
+# ``ahead``: of such a state, {statistic: reduction.Queued} of the finish
+# queued ahead (see FINISH_AHEAD; non-empty once one was queued), else None.
+Kept = collections.namedtuple('Kept', ('state', 'count', 'nlaunch', 'drop', 'serves_mean', 'ahead'))
+Kept.__new__.__defaults__ = (None,)
 
 # stats(): one StatCounter pass read for several moments (statcounter.py:30-48)
 Stats = collections.namedtuple('Stats', ('count', 'mean', 'var', 'std'))
@@ -479,7 +501,7 @@ class BoltArrayMI355X(BoltArray):
         """(array.py:43-47) -- the records stay in HBM; clears the flag and
         releases the moment states kept by mean / var / std (see KEEP_MOMENTS)."""
         self._cached = False
-        self.__dict__.pop("_kept", None)
+        self.__dict__.pop("_kept", None)   # (a finish queued ahead goes with its state: reduction.Queued)
 
     # ------------------------------------------------------------ movement
     def _permute(self, perm, split):
@@ -567,7 +589,7 @@ class BoltArrayMI355X(BoltArray):
         """Remember the state a move left (``fused``) for the last axis; it
         serves mean() too (see _kept_for)."""
         if fused:
-            self.__dict__["_kept"] = {(len(self._shape) - 1,): Kept(st[2], self._shape[-1], st[1], None, True)}
+            self.__dict__["_kept"] = {(len(self._shape) - 1,): Kept(st[2], self._shape[-1], st[1], None, True, {})}
         return self
 
     def _pitch_of(self, mv, es):
@@ -1192,10 +1214,26 @@ class BoltArrayMI355X(BoltArray):
         into the host result of the launch that kept it, no read of the array."""
         dev = entry.state.device
         be = backend_for(dev)
-        outs = reduction.outputs(be, dev, out_dtype, 1, entry.nlaunch, True)
+        ahead = entry.ahead
+        queued = ahead.pop(stat, None) if ahead else None
         with np.errstate(all="ignore"):  # pad columns' unwritten values, as in reduction.combine_moments
+            if queued is not None:
+                # finished ahead by the other statistic's call: its event, no launch
+                return reduction.finish(queued.take(), dev, plan, out_dtype, 1, entry.nlaunch, entry.drop,
+                                        event=queued.event)[0]
+            outs = reduction.outputs(be, dev, out_dtype, 1, entry.nlaunch, True)
             be.reduce_combine(stat, plan.code, entry.state, [entry.count], entry.nlaunch, outs[0][0], ocode)
-            return reduction.finish(outs, dev, plan, out_dtype, 1, entry.nlaunch, entry.drop)[0]
+            event = None
+            other = _AHEAD_OF.get(stat)
+            if FINISH_AHEAD and other is not None and ahead is not None and not ahead and outs[1] is not None:
+                odt, oc = reduction.plan_for(self, plan.axes, other)[1:]
+                outs2 = reduction.outputs(be, dev, odt, 1, entry.nlaunch, True)
+                if outs2[1] is not None:
+                    event = reduction.record_event(dev)
+                    be.reduce_combine(other, plan.code, entry.state, [entry.count], entry.nlaunch, outs2[0][0], oc)
+                    ahead[other] = reduction.Queued(outs2, reduction.record_event(dev))
+                    ahead[None] = True   # one plane per state: a later call queues no second one
+            return reduction.finish(outs, dev, plan, out_dtype, 1, entry.nlaunch, entry.drop, event=event)[0]
 
     def _reduced_moments(self, axis, want):
         """_reduced for several moments of one read: ``want`` is a subset of

@@ -13,7 +13,7 @@ from bolt_amd.mi355x import _lib
 from bolt_amd.mi355x._ops import backend_for, dtype_code
 from bolt_amd.mi355x.dist import all_gather_bytes, _empty
 from bolt_amd.mi355x.plan import padded_strides, reduce_layout, stat_dtype
-from bolt_amd.mi355x.transfer import SMALL as HOST_RESULT_MAX, finish_host_result, host_result, to_host
+from bolt_amd.mi355x.transfer import SMALL as HOST_RESULT_MAX, current_stream, finish_host_result, host_result, to_host
 
 MOMENTS = (_lib.STAT_MEAN, _lib.STAT_VAR, _lib.STAT_STD)
 # reductions whose result keeps the input dtype (numpy's same-dtype ufunc rule)
@@ -168,13 +168,44 @@ def outputs(be, dev, out_dtype, k, n, host_ok):
     return ([buf] if k == 1 else [buf[j * nb:(j + 1) * nb] for j in range(k)]), None, buf
 
 
-def finish(outs, dev, plan, out_dtype, k, n, drop=None, ctx=None):
+def record_event(dev):
+    """An event recorded behind what the current stream of ``dev`` holds so far."""
+    import torch
+    ev = torch.cuda.Event()
+    ev.record(current_stream(dev))
+    return ev
+
+
+class Queued(object):
+    """A finish queued ahead of its call (array.py's FINISH_AHEAD): outputs'
+    page-locked plane and the event behind the launch that fills it.  Dropped
+    untaken, it waits for the event first: the page-locked block must not go
+    back to the allocator while the kernel may still store into it."""
+    __slots__ = ("outs", "event")
+
+    def __init__(self, outs, event):
+        self.outs, self.event = outs, event
+
+    def take(self):
+        outs, self.outs = self.outs, None
+        return outs
+
+    def __del__(self):
+        if self.outs is not None:
+            try:
+                self.event.synchronize()
+            except Exception:   # interpreter shutdown
+                pass
+
+
+def finish(outs, dev, plan, out_dtype, k, n, drop=None, ctx=None, event=None):
     """outputs' ``k`` planes of ``n`` values, after the launch into them -> list
     of k host arrays of plan.out_shape (one stream synchronise, or one D2H),
     the pad columns' outputs dropped (``drop``, see Source).  ``ctx``: across
     ranks every rank holds the planes of its slab of the outputs; they are
     gathered (every rank takes part, one that launched nothing too) and
-    re-interleaved."""
+    re-interleaved.  ``event``: page-locked planes are complete once it is;
+    waited for instead of the stream (later launches may be queued already)."""
     _, host, buf = outs
     pshape = plan.out_shape if drop is None else drop[:3]
     shape = pshape if k == 1 else (k, n)   # the single statistic's plane is viewed as its result at once
@@ -196,7 +227,7 @@ def finish(outs, dev, plan, out_dtype, k, n, drop=None, ctx=None):
     elif type(host) is list:
         host = [finish_host_result(host[0], dev, out_dtype, (n,))] + [h.numpy().view(out_dtype) for h in host[1:]]
     else:
-        host = finish_host_result(host, dev, out_dtype, shape)
+        host = finish_host_result(host, dev, out_dtype, shape, event)
     rows = [host] if k == 1 else [host[j].reshape(pshape) for j in range(k)]
     if drop is None:
         return rows

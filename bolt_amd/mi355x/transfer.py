@@ -196,7 +196,11 @@ def current_stream(device):
     return s
 
 
-def finish_host_result(host, device, dtype, shape):
-    """Wait for the kernel that fills ``host`` and view it as the result."""
-    current_stream(device).synchronize()
+def finish_host_result(host, device, dtype, shape, event=None):
+    """Wait for the kernel that fills ``host`` -- for ``event``, recorded behind
+    it, or for the stream -- and view it as the result."""
+    if event is not None:
+        event.synchronize()
+    else:
+        current_stream(device).synchronize()
     return host.numpy().view(np.dtype(dtype)).reshape(shape)
