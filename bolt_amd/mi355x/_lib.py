@@ -15,6 +15,9 @@ STAT_MEAN, STAT_VAR, STAT_STD, STAT_SUM, STAT_MAX, STAT_MIN = range(6)
 # reduce(func) with numpy ufuncs (include/bolt_mi355x.h BM_STAT_PROD..BM_STAT_FMIN)
 STAT_PROD, STAT_LAND, STAT_LOR, STAT_BAND, STAT_BOR, STAT_BXOR, STAT_FMAX, STAT_FMIN = range(6, 14)
 MAX_COMBINE_PARTS = 256  # bm_reduce_combine's nparts limit (ranks of one merge)
+CO_COV, CO_CORR = 0, 1   # BM_CO_COV, BM_CO_CORR
+COMOMENT_MAX_SIGNALS = 4   # BM_COMOMENT_MAX_SIGNALS
+COMOMENT_MAX_PARTS = 128   # BM_COMOMENT_MAX_PARTS
 
 LIB_PATH = os.environ.get("BOLT_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "libbolt_mi355x.so")  # env: A/B builds
@@ -22,6 +25,7 @@ LIB_PATH = os.environ.get("BOLT_AMD_LIB") or os.path.join(
 # every symbol include/bolt_mi355x.h declares: name -> (restype, argtypes)
 _c = ctypes
 _i64p = _c.POINTER(_c.c_int64)
+_f64p = _c.POINTER(_c.c_double)
 SIGNATURES = {
     "bm_abi_version": (_c.c_int, []),
     "bm_last_error": (_c.c_char_p, []),
@@ -72,6 +76,13 @@ SIGNATURES = {
                                    _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "bm_reduce_combine": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _i64p, _c.c_int, _c.c_int64,
                                      _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "bm_comoment_workspace_bytes": (_c.c_int, [_c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int,
+                                               _c.POINTER(_c.c_size_t)]),
+    "bm_comoment_state": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                     _c.c_void_p, _f64p, _f64p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                     _c.c_size_t, _c.c_void_p]),
+    "bm_comoment_combine": (_c.c_int, [_c.c_int, _c.c_void_p, _i64p, _f64p, _f64p, _c.c_int, _c.c_int64,
+                                       _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "bm_comm_unique_id": (_c.c_int, [_c.c_void_p, _c.c_size_t]),
     "bm_comm_init": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_void_p, _c.c_int]),
     "bm_comm_destroy": (_c.c_int, [_c.c_void_p]),
@@ -133,6 +144,11 @@ def check(rc, what):
 def i64_array(vals):
     vals = [int(v) for v in vals]
     return (ctypes.c_int64 * max(1, len(vals)))(*vals)
+
+
+def f64_array(vals):
+    vals = [float(v) for v in vals]
+    return (ctypes.c_double * max(1, len(vals)))(*vals)
 
 
 def i32_array(vals):

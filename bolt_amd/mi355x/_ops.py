@@ -423,6 +423,44 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_standardize_apply")
 
+    def comoment_state(self, src, code, O, R, I, pitch, y, ymean, yresid, state, workspace=None):
+        """The co-moment state of one read of ``src`` ([O][R][I]; rows ``pitch``
+        elements apart when I == 1) against the K signals ``y`` (device float64,
+        K*R, signal-major) centred by the host values ``ymean``; ``yresid``:
+        the sums of the centred signals (bm_comoment_state).  ``state``: (2 + K)
+        float64 planes of O*I values.  ``workspace``: a tensor to use instead
+        of one of bm_comoment_workspace_bytes."""
+        import torch
+        K = len(ymean)
+        if workspace is None:
+            key = ("comoment", code, O, R, I, K)
+            nws = self._ws.get(key)
+            if nws is None:
+                n = ctypes.c_size_t(0)
+                _lib.check(self.lib.bm_comoment_workspace_bytes(code, O, R, I, K, ctypes.byref(n)),
+                           "bm_comoment_workspace_bytes")
+                nws = self._ws[key] = n.value
+            workspace = torch.empty(nws, dtype=torch.uint8, device=src.device) if nws else None
+        nws = workspace.numel() if workspace is not None else 0
+        rc = self.lib.bm_comoment_state(src.data_ptr(), code, O, R, I, pitch, y.data_ptr(), _lib.f64_array(ymean),
+                                        _lib.f64_array(yresid), K, state.data_ptr(),
+                                        workspace.data_ptr() if workspace is not None else None, nws,
+                                        raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_comoment_state")
+
+    def comoment_combine(self, what, states, counts, ymean, ym2, nout, K, out, out_code):
+        """``len(counts)`` comoment_state states (part-major) merged in part
+        order and finalised to cov / corr (``what``: _lib.CO_COV / CO_CORR) into
+        ``out``: K planes of ``nout`` values.  ``ymean`` / ``ym2``: each part's
+        mean and sum of squared deviations of its slice of every signal,
+        part-major (bm_comoment_combine)."""
+        rc = self.lib.bm_comoment_combine(what, states.data_ptr(), _lib.i64_array(counts), _lib.f64_array(ymean),
+                                          _lib.f64_array(ym2), len(counts), nout, K, out.data_ptr(), out_code,
+                                          raw_stream(states.device))
+        if rc:
+            _lib.check(rc, "bm_comoment_combine")
+
     def state_bytes(self, stat, code, nout):
         n = ctypes.c_size_t(0)
         _lib.check(self.lib.bm_reduce_state_bytes(stat, code, nout, ctypes.byref(n)), "bm_reduce_state_bytes")

@@ -1436,6 +1436,146 @@ class BoltArrayMI355X(BoltArray):
         throughout.  An addition to the reference's API."""
         return self._standardized(axis, True)
 
+    def _comoment(self, y, axis, keepdims, what):
+        """cov / corr (``what``: _lib.CO_COV / CO_CORR) of every record over
+        ``axis`` with the signal(s) ``y`` -> host result.
+
+        Planned with reduction.plan_for / source like _reduced, and what it
+        costs: one read of the array per batch of _lib.COMOMENT_MAX_SIGNALS
+        signals (bm_comoment_state), then bm_comoment_combine of one part into
+        the host result.  Rows over the last axis are read in place, padded or
+        not; columns over padded rows too (the pad columns' outputs dropped);
+        reduced axes that are not one block are permuted to the front first
+        (``y`` is flattened in C order of the sorted reduced axes, so it
+        indexes the permuted rows unchanged); every axis of a padded array
+        compacts, as sum() does.  Across ranks: the sharded axis kept, every
+        rank finishes its slab's outputs and they are gathered; reduced, every
+        rank's state over its slice of ``y`` is gathered and merged in rank
+        order (at most _lib.COMOMENT_MAX_PARTS ranks).  Moment states
+        (KEEP_MOMENTS) are neither used nor left; nothing is cached."""
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        axes = tuple(sorted(set(int(a) for a in ax)))
+        rshape = tuple(int(self._shape[a]) for a in axes)
+        try:
+            ys = np.asarray(y)
+        except Exception:
+            raise ValueError("cov / corr: the signal is not array-like")
+        if ys.dtype.kind not in "biuf":
+            raise ValueError("cov / corr: the signal must be real (bool, int or float), got dtype %s" % ys.dtype)
+        one = ys.shape == rshape
+        if not one and not (ys.ndim == len(rshape) + 1 and ys.shape[1:] == rshape and ys.shape[0] >= 1):
+            raise ValueError("cov / corr: a signal of shape %s or (K,) + %s with K >= 1 is needed for axis %s, got %s"
+                             % (rshape, rshape, axes, ys.shape))
+        ys = np.ascontiguousarray(ys, dtype=np.float64).reshape((1 if one else ys.shape[0],) + rshape)
+        if not np.isfinite(ys).all():
+            raise ValueError("cov / corr: the signal holds a non-finite value")
+        K = ys.shape[0]
+        plan, out_dtype, ocode = reduction.plan_for(self, ax, reduction.COMOMENT)
+        if self._ctx.world_size > _lib.COMOMENT_MAX_PARTS and 0 in axes:
+            raise NotImplementedError("cov / corr over the sharded axis merge at most %d ranks (got %d)"
+                                      % (_lib.COMOMENT_MAX_PARTS, self._ctx.world_size))
+        if self._nrecords(ax) == 0:
+            planes = [np.full(plan.out_shape, np.nan, dtype=out_dtype) for _ in range(K)]
+        else:
+            planes = []
+            for k0 in range(0, K, _lib.COMOMENT_MAX_SIGNALS):
+                planes += self._comoment_batch(plan, out_dtype, ocode, ys[k0:k0 + _lib.COMOMENT_MAX_SIGNALS], what)
+        vs = self._aligned_vshape(ax)
+        res = []
+        for arr in planes:
+            if vs is not None:
+                arr = arr.reshape(vs)
+            if keepdims:
+                for i in ax:
+                    arr = np.expand_dims(arr, axis=i)
+            res.append(arr)
+        arr = res[0] if one else np.stack(res)
+        if arr.ndim == 0:
+            arr = arr[()]
+        return BoltArrayLocal(arr).toscalar()
+
+    def _comoment_batch(self, plan, out_dtype, ocode, ys, what):
+        """_comoment for the Kb <= _lib.COMOMENT_MAX_SIGNALS signals ``ys``
+        ((Kb,) + the reduced extents) -> list of Kb host arrays of plan.out_shape."""
+        Kb, code = ys.shape[0], plan.code
+        src = reduction.source(self, plan, moments=False)
+        nlaunch, drop = src.nlaunch, src.drop
+        dev = src.buf.device
+        be = backend_for(dev)
+        single = plan.world == 1
+        if single or 0 not in plan.axes:
+            # every output lives on this rank (or this rank's slab of them);
+            # every reduced record lies whole on it, so the signals are whole too
+            run = nlaunch and plan.nloc
+            if run:
+                # the read is launched first; what only the finish needs is
+                # worked out, and its buffers made, while the read runs
+                yk = ys.reshape(Kb, -1)
+                ymean, yresid, yc = reduction.signal_centre(yk)
+                state = _empty((2 + Kb) * nlaunch * 8, dev)
+                with np.errstate(all="ignore"):  # a numpy executor on pad columns' unwritten values (dropped later)
+                    reduction.comoment_state(be, src, self._dtype, code, yk, ymean, yresid, state)
+            # (the Kb planes are stored by one launch, so they share one buffer:
+            # page-locked only when all of them fit the zero-copy limit)
+            outs = reduction.outputs(be, dev, out_dtype, Kb, nlaunch, single and run and
+                                     Kb * nlaunch * out_dtype.itemsize <= reduction.HOST_RESULT_MAX)
+            if run:
+                with np.errstate(all="ignore"):
+                    reduction.comoment_combine(be, what, state, [src.R], [ymean], [reduction.signal_m2(yc, yresid)],
+                                               nlaunch, Kb, outs[2] if outs[2] is not None else outs[1], out_dtype,
+                                               ocode)
+            return reduction.finish(outs, dev, plan, out_dtype, Kb, nlaunch, drop, None if single else self._ctx)
+        # the sharded axis is reduced: one state per rank over its slice of the
+        # signals (zeroes where its slab is empty), gathered and merged in rank order
+        if plan.nout == 0:  # e.g. axis 0 of (4, 0, 3): nothing to merge
+            return [np.empty(plan.out_shape, out_dtype) for _ in range(Kb)]
+        ctx = self._ctx
+        bounds = ctx.bounds(plan.shape[0])
+        per = int(np.prod([plan.shape[i] for i in plan.axes if i != 0], dtype=np.int64))
+        counts = [(hi - lo) * per for lo, hi in bounds]
+        parts = [reduction.signal_centre(ys[:, lo:hi].reshape(Kb, -1)) for lo, hi in bounds]
+        sbytes = (2 + Kb) * plan.nout * 8
+        state = _empty(sbytes, dev)
+        if plan.nloc:
+            lo, hi = bounds[ctx.rank]
+            mine = parts[ctx.rank]
+            reduction.comoment_state(be, src, self._dtype, code, ys[:, lo:hi].reshape(Kb, -1), mine[0], mine[1],
+                                     state)
+        else:
+            state.zero_()
+        states = all_gather_bytes(ctx, state, [sbytes] * plan.world)
+        outs = reduction.outputs(be, dev, out_dtype, Kb, plan.nout, False)
+        reduction.comoment_combine(be, what, states, counts, [p[0] for p in parts],
+                                   [reduction.signal_m2(p[2], p[1]) for p in parts],
+                                   plan.nout, Kb, outs[2], out_dtype, ocode)
+        return reduction.finish(outs, dev, plan, out_dtype, Kb, plan.nout)
+
+    def cov(self, y, axis=None, keepdims=False):
+        """Population covariance (ddof = 0, as var / std) of every record over
+        ``axis`` (None: every axis; taken as mean() takes it) with the signal
+        ``y``: mean((x - mean(x)) (y - mean(y))).  ``y`` is array-like and real,
+        of the reduced axes' extents in ascending axis order -- or (K,) + those
+        for K >= 1 signals, which share reads of the array, four signals a read
+        (more signals read it again per four); anything else raises ValueError
+        before any device work.  The result is a host result as stats() returns
+        its fields, of the kept axes' shape ((K,) + that for K signals;
+        ``keepdims`` re-inserts the reduced axes after the K axis) and the
+        statistics dtype (float16 / float32 keep theirs, every other dtype
+        gives float64).  The arithmetic is float64, rounded once; a constant
+        record or signal gives 0; a nan in a record reaches its outputs only;
+        no records give nan.  Plane k of a K-signal call has the bytes of the
+        one-signal call with y[k].  An addition to the reference's API."""
+        return self._comoment(y, axis, keepdims, _lib.CO_COV)
+
+    def corr(self, y, axis=None, keepdims=False):
+        """Pearson correlation cov(y) / (std_x std_y) of every record over
+        ``axis`` with the signal(s) ``y``, taken and returned as cov() takes and
+        returns them; clamped to [-1, 1] before the one rounding, as
+        numpy.corrcoef does.  A record or a signal of zero variance gives nan.
+        An addition to the reference's API."""
+        return self._comoment(y, axis, keepdims, _lib.CO_CORR)
+
     def _stat(self, axis=None, func=None, name=None, keepdims=False):
         """Statistic over ``axis`` (array.py:284-334); results are host arrays / scalars."""
         if name and not func:

@@ -1,7 +1,7 @@
 """Mechanics of the statistics: how the reduced axes of an array lie in HBM and
 what is launched to reduce over them.  One plan, one source, one finish, for
-array.py's _reduced (one statistic), _reduced_moments (stats()) and
-_standardized (center / zscore).  The rules -- what is kept, padded or fused,
+array.py's _reduced (one statistic), _reduced_moments (stats()),
+_standardized (center / zscore) and _comoment (cov / corr).  The rules -- what is kept, padded or fused,
 and their switches -- stay in array.py; this module never imports it and is
 handed the array.
 """
@@ -20,6 +20,7 @@ MOMENTS = (_lib.STAT_MEAN, _lib.STAT_VAR, _lib.STAT_STD)
 _KEEP_DTYPE = (_lib.STAT_SUM, _lib.STAT_MAX, _lib.STAT_MIN, _lib.STAT_PROD, _lib.STAT_BAND,
                _lib.STAT_BOR, _lib.STAT_BXOR, _lib.STAT_FMAX, _lib.STAT_FMIN)
 STANDARDIZE = 'standardize'  # plan_for's statistic for center / zscore: the dtype of ``record - 0.0``
+COMOMENT = 'comoment'  # plan_for's statistic for cov / corr: the statistics dtype of the outputs
 STATS_FIELDS = ('mean', 'var', 'std')  # the order of bm_reduce_moments' outputs
 
 # What reducing ``axes`` (sorted) of an array needs, from its shapes and dtype
@@ -41,7 +42,7 @@ _tuple_new = tuple.__new__
 
 def plan_for(arr, axis, stat):
     """-> (the Plan of reducing ``axis`` of ``arr``, the result dtype of
-    ``stat`` -- a _lib.STAT_* or STANDARDIZE -- and its code)."""
+    ``stat`` -- a _lib.STAT_*, STANDARDIZE or COMOMENT -- and its code)."""
     lshape = arr._local_shape
     key = (lshape, tuple(axis), arr._dtype, arr._shape, arr._ctx.world_size)
     plan = _PLANS.get(key)
@@ -275,6 +276,106 @@ def launch_moments(be, src, es, code, ocode, want, planes):
     with np.errstate(all="ignore"):  # pad columns' unwritten values, as in combine_moments
         be.reduce_state(_lib.STAT_VAR, buf, code, O, R, I, state)
     combine_moments(be, code, ocode, want, state, [R], O * I, planes)
+
+
+def signal_centre(ys):
+    """What the state launch needs of ``ys``, (K, n) float64 signals -> (mean,
+    resid, centred): the float64 mean every signal is centred by (a constant
+    signal's is its value, so it centres to exact zeros), the sum of the
+    centred float64 values -- the mean's rounding residue, which the state is
+    corrected by, so the mean need not be better than float64's -- K floats
+    each, and the centred values (the differences the kernels form)."""
+    K, n = ys.shape
+    if n == 0:
+        return [0.0] * K, [0.0] * K, ys
+    mean = np.where(np.ptp(ys, axis=1) == 0.0, ys[:, 0], ys.mean(axis=1))
+    c = ys - mean[:, None]
+    return mean.tolist(), c.sum(axis=1).tolist(), c
+
+
+def signal_m2(c, resid):
+    """The signals' sums of squared deviations from signal_centre's centred
+    values and residues (the finish needs them, not the state launch)."""
+    n = c.shape[1]
+    if n == 0:
+        return [0.0] * c.shape[0]
+    return (np.einsum("ij,ij->i", c, c) - np.square(resid) / n).tolist()
+
+
+def comoment_state(be, src, dtype, code, ys, ymean, yresid, state):
+    """The co-moment state of one read of ``src`` against the (K, R) float64
+    signals ``ys`` into ``state``: (2 + K) float64 planes of src.nlaunch values,
+    mean, M2, then C_k = sum (x - mean)(y_k - ymean_k) (bm_comoment_state)."""
+    import torch
+    buf, O, R, I, pitch = src[:5]
+    K = len(ymean)
+    if hasattr(be, "comoment_state"):
+        yd = torch.from_numpy(np.ascontiguousarray(ys, dtype=np.float64).reshape(-1))
+        if buf.device.type == "cuda":
+            # page-locked + non-blocking: the upload queues behind earlier
+            # kernels; the launch that reads it follows on the same stream
+            yd = yd.pin_memory().to(buf.device, non_blocking=True)
+        return be.comoment_state(buf, code, O, R, I, pitch, yd, ymean, yresid, state)
+    # an executor without the entry points (the CPU test executor): torch
+    # float64 arithmetic on views of the bytes, padded rows through a strided view
+    from bolt_amd.mi355x import functional as F
+    es = np.dtype(dtype).itemsize
+    if pitch != R:
+        x = F.view(buf[:O * pitch * es], (O, pitch), dtype)[:, :R].unsqueeze(2)
+    else:
+        x = F.view(buf, (O, R, I), dtype)
+    x = x.to(torch.float64)
+    d = x - x.mean(dim=1, keepdim=True)
+    st = F.view(state, (2 + K, O * I), np.float64)
+    st[0] = x.mean(dim=1).reshape(-1)
+    st[1] = (d * d).sum(dim=1).reshape(-1)
+    yc = torch.from_numpy(ys - np.asarray(ymean, dtype=np.float64)[:, None]).to(buf.device)
+    for k in range(K):
+        st[2 + k] = (d * yc[k].reshape(1, R, 1)).sum(dim=1).reshape(-1)
+
+
+def comoment_combine(be, what, states, counts, ymean, ym2, nout, K, out, out_dtype, ocode):
+    """comoment_state states of ``len(counts)`` parts (part-major), merged in
+    part order and finalised to cov / corr into ``out``, K planes of ``nout``
+    values; ``ymean`` / ``ym2``: per part, the K means and sums of squared
+    deviations of its slice of the signals (bm_comoment_combine)."""
+    flat_m = [v for part in ymean for v in part]
+    flat_q = [v for part in ym2 for v in part]
+    if hasattr(be, "comoment_combine"):
+        return be.comoment_combine(what, states, counts, flat_m, flat_q, nout, K, out, ocode)
+    # the same merge in torch float64 (an executor without the entry points)
+    import torch
+    from bolt_amd.mi355x import functional as F
+    st = F.view(states, (len(counts), 2 + K, nout), np.float64)
+    n, m, q, C = 0.0, None, None, None
+    ym, yq = [0.0] * K, [0.0] * K
+    for p, c in enumerate(counts):
+        c = float(c)
+        if c <= 0:
+            continue
+        if n == 0.0:
+            n, m, q, C = c, st[p, 0].clone(), st[p, 1].clone(), st[p, 2:].clone()
+            ym, yq = list(ymean[p]), list(ym2[p])
+            continue
+        tot = n + c
+        d = st[p, 0] - m
+        m = m + d * (c / tot)
+        q = q + st[p, 1] + d * d * (n * c / tot)
+        for k in range(K):
+            dy = ymean[p][k] - ym[k]
+            C[k] = C[k] + st[p, 2 + k] + d * (dy * (n * c / tot))
+            ym[k] += dy * (c / tot)
+            yq[k] += ym2[p][k] + dy * dy * (n * c / tot)
+        n = tot
+    if n == 0.0:
+        r = torch.full((K, nout), float("nan"), dtype=torch.float64, device=states.device)
+    elif what == _lib.CO_COV:
+        r = C / n
+    else:
+        den = q.reshape(1, nout) * torch.tensor(yq, dtype=torch.float64, device=states.device).reshape(K, 1)
+        r = torch.where(den > 0, torch.clamp(C / torch.sqrt(den), -1.0, 1.0),
+                        torch.full_like(den, float("nan")))   # no variance, no correlation
+    F.view(out, (K, nout), out_dtype).copy_(r.to(F.torch_dtype(out_dtype)))
 
 
 def merge_equal_counts(planes, Rl, nrows):

@@ -431,6 +431,80 @@ int bm_reduce_combine_moments(int in_dtype, const void *states,
                               int out_dtype, void *stream);
 
 /*
+ * cov() / corr(): the co-moment of every record with fixed signals.
+ * No reference call site: an API addition (the reference has neither method;
+ * its users correlate on the host, record by record, through map()).  The
+ * state extends the StatCounter of one partition (n, mu, m2:
+ * bolt/spark/statcounter.py:30-48) by one co-moment per signal, and the merge
+ * extends StatCounter.combine (bolt/spark/statcounter.py:67-99).
+ */
+#define BM_COMOMENT_MAX_SIGNALS 4   /* signals per call: one read of the array serves them all */
+#define BM_COMOMENT_MAX_PARTS 128   /* parts per bm_comoment_combine */
+#define BM_CO_COV 0    /* population covariance C / n (ddof = 0, as BM_STAT_VAR) */
+#define BM_CO_CORR 1   /* Pearson r = C / sqrt(M2_x M2_y), clamped to [-1, 1]  */
+
+/*
+ * bm_comoment_workspace_bytes -- scratch bm_comoment_state needs for this
+ * layout and K (the chunks' partial sums when the reduced extent is split;
+ * 0 when it is not); it holds for every alignment of src and every pitch.  No reference call site: an API addition.  Monotone in
+ * K; any of O, R, I == 0 gives 0.
+ */
+int bm_comoment_workspace_bytes(int in_dtype, int64_t O, int64_t R, int64_t I,
+                                int K, size_t *bytes);
+
+/*
+ * bm_comoment_state -- one read of src ([O][R][I] as bm_reduce; with I == 1
+ * rows are row_pitch >= R elements apart and the pad is never read, otherwise
+ * row_pitch = R) into the co-moment state of its O*I records: (2 + K) float64
+ * planes of O*I values, mean_x, M2_x, then for each signal k
+ *   C_k = sum_r (x_r - mean_x) (y_k[r] - ymean_k).
+ * No reference call site: an API addition; the state is the StatCounter's
+ * (n = R, mu, m2) that statcounter.py:67-99 merges, with C_k added.
+ * y: device memory, K*R float64, signal-major.  ymean (host, K values): what
+ * each signal is centred by, the caller's float64 mean of its R values;
+ * yresid (host, K values, or NULL for zeros): sum_r (y_k[r] - ymean_k), the
+ * rounding residue of that mean, which the state is corrected by.  Every
+ * accumulation is float64 about the record's first element, summed in a fixed
+ * order (lanes, row phases, chunks: see bm_comoment.hip): the same input gives
+ * the same bytes, and plane k has the bytes of the one-signal call with y_k.
+ * workspace: bm_comoment_workspace_bytes (BM_E_WS if smaller).  A nan in a
+ * record reaches that record's values only.  Any of O, R, I == 0 stores
+ * nothing.  Arguments are checked before any launch: null pointers, a bad
+ * dtype, negative extents, a pitch below R or a pitch with I > 1, K outside
+ * 1..BM_COMOMENT_MAX_SIGNALS give BM_E_ARG.
+ */
+int bm_comoment_state(const void *src, int in_dtype, int64_t O, int64_t R,
+                      int64_t I, int64_t row_pitch, const double *y,
+                      const double *ymean, const double *yresid, int K,
+                      void *state, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
+/*
+ * bm_comoment_combine -- nparts states of bm_comoment_state (back to back,
+ * part-major) merged in part order with the pairwise update of
+ * statcounter.py:67-99, (mean, M2) as bm_reduce_combine merges them and
+ *   C = Ca + Cb + (mean_xb - mean_xa) (ymean_b - ymean_a) na nb / (na + nb),
+ * then finalised into K planes of nout values of out_dtype:
+ *   what = BM_CO_COV:  C / n;
+ *   what = BM_CO_CORR: C / sqrt(M2_x M2_y), clamped to [-1, 1] before the one
+ *                      rounding; nan unless M2_x M2_y > 0 (a record or a
+ *                      signal of zero variance, whatever rounding left in C).
+ * No reference call site: an API addition.  counts[nparts] (parts of count 0
+ * are skipped; all 0: nan), ymean[nparts*K] and ym2[nparts*K] (each part's
+ * own mean and sum of squared deviations of its slice of signal k, part-major)
+ * are host arrays; the signals' side of the merge runs on the host.  out may
+ * be a bm_host_writable buffer.  A local call is bm_comoment_state followed by
+ * this with one part.  nparts <= BM_COMOMENT_MAX_PARTS.  nout == 0 stores
+ * nothing.  BM_E_ARG for null pointers, what out of range, an out_dtype that
+ * is not a statistics dtype (float16 / float32 / float64), K outside
+ * 1..BM_COMOMENT_MAX_SIGNALS, nparts out of range, a negative count or nout.
+ */
+int bm_comoment_combine(int what, const void *states, const int64_t *counts,
+                        const double *ymean, const double *ym2, int nparts,
+                        int64_t nout, int K, void *out, int out_dtype,
+                        void *stream);
+
+/*
  * ---------------------------------------------------------------------------
  * Multi-GPU record exchange over RCCL (xGMI), one process per GPU.
  *
