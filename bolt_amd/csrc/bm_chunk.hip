@@ -25,6 +25,7 @@
 // more blocks per CU.
 // Larger records use the direct form (map lookups straight from HBM/L2).
 #include "bm_common.h"
+#include "bm_host.h"
 #include "../../include/bolt_mi355x.h"
 
 #include <algorithm>
@@ -599,12 +600,7 @@ extern "C" int bm_record_gather_masked(const void *src_, void *dst_, int64_t nre
       default: k_recmap_direct<8><<<(int)g, kCThreads, 0, st>>>(src, dst, map, src_rec, total, f); break;
     }
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("bm_record_gather: launch failed: %s", hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
+  return check_launch("bm_record_gather");
 }
 
 extern "C" int bm_record_scatter(const void *src_, void *dst_, int64_t nrec, int64_t src_rec, int64_t group,
@@ -637,12 +633,7 @@ extern "C" int bm_record_scatter(const void *src_, void *dst_, int64_t nrec, int
     case 4: launch_scatter<4>(src, dst, map_a, map_b, nrec, src_rec, group, dst_group_stride, vec, st); break;
     default: launch_scatter<8>(src, dst, map_a, map_b, nrec, src_rec, group, dst_group_stride, vec, st); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("bm_record_scatter: launch failed: %s", hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
+  return check_launch("bm_record_scatter");
 }
 
 extern "C" int bm_record_runs(const void *src_, void *dst_, int64_t nrec, int64_t src_rec, int64_t group,
@@ -680,10 +671,5 @@ extern "C" int bm_record_runs(const void *src_, void *dst_, int64_t nrec, int64_
     case 2: launch_runs<2>(src, dst, runs, nruns, nrec, sv, group, gv, tiled, st); break;
     default: launch_runs<1>(src, dst, runs, nruns, nrec, sv, group, gv, tiled, st); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("bm_record_runs: launch failed: %s", hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
+  return check_launch("bm_record_runs");
 }

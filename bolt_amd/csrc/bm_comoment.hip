@@ -47,6 +47,7 @@
 //   whatever K is (explicit fma, no contraction across signals): plane k of a
 //   K-signal call has the bits of the one-signal call.  No float atomics.
 #include "bm_common.h"
+#include "bm_host.h"
 #include "bm_wave.h"
 #include "../../include/bolt_mi355x.h"
 
@@ -57,7 +58,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int64_t kMaxBlocks = 0xffffffffLL / kThreads;  // HIP launch limit: grid * block threads < 2^32
 constexpr int KMAX = BM_COMOMENT_MAX_SIGNALS;
 constexpr int kMaxParts = BM_COMOMENT_MAX_PARTS;  // parts per bm_comoment_combine: the merge tables are kernel arguments
 constexpr int kMaxVec = 8;      // elements per vector at most, as bm_standardize.hip
@@ -73,18 +73,6 @@ constexpr int rows_waves(int KT) { return KT > 2 ? 8 : 4; }
 constexpr int64_t kColsBlocks = 2048;
 constexpr int kColsTcv = 64;
 constexpr int kColsUnroll = 4;
-
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-int dtype_size(int dt) {
-  switch (dt) {
-    case BM_BOOL: case BM_U8: case BM_I8: return 1;
-    case BM_U16: case BM_I16: case BM_F16: return 2;
-    case BM_U32: case BM_I32: case BM_F32: return 4;
-    case BM_U64: case BM_I64: case BM_F64: return 8;
-    default: return 0;
-  }
-}
 
 // the signals' host statistics, kernel arguments
 struct YStat {
@@ -237,16 +225,7 @@ __global__ void __launch_bounds__(64 * rows_waves(KT))
 }
 
 // ------------------------------------------------------------------ cols --
-// blockIdx.x with the blocks the hardware deals to one XCD (every 8th)
-// remapped to consecutive indices, a bijection of the grid: each XCD reads one
-// contiguous range of every row (the rule of bm_reduce.hip's xcd_block)
-__device__ __forceinline__ uint64_t xcd_block() {
-  uint64_t bid = blockIdx.x;
-  const uint64_t g8 = gridDim.x / 8 * 8;
-  if (bid < g8) bid = (bid % 8) * (g8 / 8) + bid / 8;
-  return bid;
-}
-
+// (the XCD-aware block order, xcd_block, is in bm_wave.h)
 struct ColsDesc {
   int64_t O, R, I;
   int64_t rchunk, nchunks;
@@ -479,11 +458,10 @@ struct CoPlan {
 CoPlan plan_comoment(int dt, int64_t O, int64_t R, int64_t I, const void *src, int64_t P) {
   CoPlan p{};
   const int es = dtype_size(dt);
-  int vec = std::min(16 / es, kMaxVec);
+  const int cap = std::min(16 / es, kMaxVec);
   if (I == 1) {
     p.rows = true;
-    while (vec > 1 && !(R % vec == 0 && P % vec == 0 && (uintptr_t)src % (size_t)(vec * es) == 0)) vec >>= 1;
-    p.vec = vec;
+    p.vec = pick_vec(cap, {R, P}, {{src, es}});
     p.rchunk = kRowsChunk;
     p.nchunks = cdiv(R, kRowsChunk);
     // rows per wave: up to kRowsWalk, while the device still gets 2048 blocks
@@ -493,10 +471,9 @@ CoPlan plan_comoment(int dt, int64_t O, int64_t R, int64_t I, const void *src, i
     // the chunks of R are planned for the widest vector I allows, whatever
     // the pointer allows: the workspace (sized without the pointer) and the
     // order of the chunk sums do not depend on the source's alignment
-    while (vec > 1 && I % vec != 0) vec >>= 1;
     int64_t nch = 1;
     {
-      const int64_t ncolv = I / vec;
+      const int64_t ncolv = I / pick_vec(cap, {I}, {});
       int tcv = 1;
       while (tcv < kColsTcv && tcv < ncolv) tcv <<= 1;
       const int64_t blocks = O * cdiv(ncolv, tcv);
@@ -506,9 +483,8 @@ CoPlan plan_comoment(int dt, int64_t O, int64_t R, int64_t I, const void *src, i
       }
       nch = std::min<int64_t>(nch, 65535);
     }
-    while (vec > 1 && (uintptr_t)src % (size_t)(vec * es) != 0) vec >>= 1;
-    p.vec = vec;
-    const int64_t ncolv = I / vec;
+    p.vec = pick_vec(cap, {I}, {{src, es}});
+    const int64_t ncolv = I / p.vec;
     int tcv = 1;
     while (tcv < kColsTcv && tcv < ncolv) tcv <<= 1;
     p.tcv = tcv;
@@ -534,23 +510,18 @@ void launch_v(const CoPlan &p, const void *src, const double *y, int64_t O, int6
     d.fchunks = make_fastdiv((uint64_t)p.nchunks);
     constexpr int kW = rows_waves(KT);
     d.nitems = cdiv(O, (int64_t)kW * p.walk) * p.nchunks;
-    constexpr int64_t maxb = 0xffffffffLL / (64 * kW);  // grid * block threads < 2^32
-    for (int64_t b0 = 0; b0 < d.nitems; b0 += maxb) {
+    for_block_runs(d.nitems, 64 * kW, [&](int64_t b0, int g) {
       d.item0 = b0;
-      const int g = (int)std::min<int64_t>(maxb, d.nitems - b0);
       k_co_rows<T, VEC, KT><<<g, 64 * kW, 0, st>>>(s, y, d, ys, state, part);
-    }
+    });
   } else {
     ColsDesc d{};
     d.O = O; d.R = R; d.I = I; d.rchunk = p.rchunk; d.nchunks = p.nchunks; d.tcv = p.tcv; d.nph = p.nph; d.K = K;
     d.ntc = make_fastdiv((uint64_t)p.ntc);
-    const int64_t bx = O * p.ntc;
-    const int64_t per = std::max<int64_t>(1, kMaxBlocks / p.nchunks);
-    for (int64_t t0 = 0; t0 < bx; t0 += per) {
+    for_tile_runs(O * p.ntc, p.nchunks, kThreads, [&](int64_t t0, dim3 grid) {
       d.tile0 = t0;
-      dim3 grid((unsigned)std::min<int64_t>(per, bx - t0), (unsigned)p.nchunks);
       k_co_cols<T, VEC, KT><<<grid, kThreads, 0, st>>>(s, y, d, ys, state, part);
-    }
+    });
   }
 }
 
@@ -559,42 +530,6 @@ template <typename T, int VEC, typename... A> void launch_k(int K, A... a) {
   if (K == 1) launch_v<T, VEC, 1>(a...);
   else if (K == 2) launch_v<T, VEC, 2>(a...);
   else launch_v<T, VEC, 4>(a...);
-}
-
-template <typename T, typename... A> void launch_t(int vec, int K, A... a) {
-  switch (vec) {
-    case 8: if constexpr (8 * sizeof(T) <= 16) { launch_k<T, 8>(K, a...); } break;
-    case 4: if constexpr (4 * sizeof(T) <= 16) { launch_k<T, 4>(K, a...); } break;
-    case 2: if constexpr (2 * sizeof(T) <= 16) { launch_k<T, 2>(K, a...); } break;
-    default: launch_k<T, 1>(K, a...); break;
-  }
-}
-
-// (bool through the uint8 kernels: its values are 0 / 1)
-template <typename... A> void launch_dt(int dt, int vec, int K, A... a) {
-  switch (dt) {
-    case BM_BOOL:
-    case BM_U8: launch_t<uint8_t>(vec, K, a...); break;
-    case BM_I8: launch_t<int8_t>(vec, K, a...); break;
-    case BM_U16: launch_t<uint16_t>(vec, K, a...); break;
-    case BM_I16: launch_t<int16_t>(vec, K, a...); break;
-    case BM_U32: launch_t<uint32_t>(vec, K, a...); break;
-    case BM_I32: launch_t<int32_t>(vec, K, a...); break;
-    case BM_U64: launch_t<uint64_t>(vec, K, a...); break;
-    case BM_I64: launch_t<int64_t>(vec, K, a...); break;
-    case BM_F16: launch_t<_Float16>(vec, K, a...); break;
-    case BM_F32: launch_t<float>(vec, K, a...); break;
-    default: launch_t<double>(vec, K, a...); break;
-  }
-}
-
-int check_launch(const char *who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
 }
 
 int check_layout(const char *who, int in_dtype, int64_t O, int64_t R, int64_t I, int K) {
@@ -646,7 +581,7 @@ extern "C" int bm_comoment_state(const void *src, int in_dtype, int64_t O, int64
     bm_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
     return BM_E_WS;
   }
-  if (p.nchunks > 1 && cdiv(nout, kThreads) > kMaxBlocks) {
+  if (p.nchunks > 1 && cdiv(nout, kThreads) > max_blocks(kThreads)) {
     bm_set_error("%s: %lld outputs of a chunked reduction exceed one launch", who, (long long)nout);
     return BM_E_ARG;
   }
@@ -656,7 +591,13 @@ extern "C" int bm_comoment_state(const void *src, int in_dtype, int64_t O, int64
     ys.resid[k] = yresid ? yresid[k] : 0.0;
   }
   hipStream_t st = (hipStream_t)stream;
-  launch_dt(in_dtype, p.vec, K, p, src, y, O, R, row_pitch, I, K, ys, (double *)state, (double *)workspace, st);
+  for_dtype(in_dtype, [&](auto t) {  // (a dtype code: check_layout)
+    typedef typename decltype(t)::type T;
+    for_vec<T, kMaxVec>(p.vec, [&](auto v) {
+      launch_k<T, decltype(v)::value>(K, p, src, y, O, R, row_pitch, I, K, ys, (double *)state, (double *)workspace,
+                                      st);
+    });
+  });
   if (p.nchunks > 1) {
     MergeDesc m{};
     m.nout = nout; m.nchunks = p.nchunks; m.n = (double)R; m.K = K;
@@ -712,7 +653,7 @@ extern "C" int bm_comoment_combine(int what, const void *states, const int64_t *
   }
   for (int k = 0; k < K; ++k) d.m2y[k] = yq[k];
   const int64_t blocks = cdiv(nout, kThreads);
-  if (blocks > kMaxBlocks) { bm_set_error("%s: %lld outputs exceed one launch", who, (long long)nout); return BM_E_ARG; }
+  if (blocks > max_blocks(kThreads)) { bm_set_error("%s: %lld outputs exceed one launch", who, (long long)nout); return BM_E_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const double *s = (const double *)states;
   if (out_dtype == BM_F16) k_co_combine<_Float16><<<(int)blocks, kThreads, 0, st>>>(s, d, (_Float16 *)out);

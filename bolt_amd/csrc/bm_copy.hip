@@ -21,6 +21,7 @@
 //
 // All are HBM-bound; algorithmic bytes = 2 * N * elem_bytes.
 #include "bm_common.h"
+#include "bm_host.h"
 #include "bm_wave.h"
 #include "../../include/bolt_mi355x.h"
 
@@ -1234,12 +1235,7 @@ int copy_strided(const void *src_, void *dst_, int ndim, const int64_t *shape, c
     }
   }
   if (rc != BM_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("bm_copy_strided: launch failed: %s", hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
+  return check_launch("bm_copy_strided");
 }
 
 // the checks bm_copy_strided_moments and its workspace query share

@@ -11,6 +11,7 @@
 // the row and both base pointers; HBM-bound, algorithmic bytes =
 // 2 * n_outer * n_idx * row_bytes (+ 8 B per index, read once per row).
 #include "bm_common.h"
+#include "bm_host.h"
 #include "../../include/bolt_mi355x.h"
 
 namespace {
@@ -72,10 +73,5 @@ extern "C" int bm_gather_rows(const void *src, void *dst, int64_t n_outer, int64
     case 2: launch<2>(s, d, idx, n_outer, src_rows, row_bytes, n_idx, st); break;
     default: launch<1>(s, d, idx, n_outer, src_rows, row_bytes, n_idx, st); break;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("bm_gather_rows: launch failed: %s", hipGetErrorString(e));
-    return BM_E_HIP;
-  }
-  return BM_OK;
+  return check_launch("bm_gather_rows");
 }

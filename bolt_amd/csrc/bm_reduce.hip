@@ -27,6 +27,7 @@
 //   truncated to the input width; over bool an OR.
 // All are HBM-bound: algorithmic bytes = N*elem_bytes + nout*out_bytes.
 #include "bm_common.h"
+#include "bm_host.h"
 #include "bm_wave.h"
 #include "../../include/bolt_mi355x.h"
 
@@ -35,7 +36,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int64_t kMaxBlocks = 0xffffffffLL / kThreads;  // HIP launch limit: grid * block threads < 2^32
 // Shipped parameters (the A/B runs that chose them are cited; the rejected
 // values live in git history and tools/microbench/):
 // rows in flight per lane in the column reductions: 8 over 4 +1.2-1.4% on the
@@ -409,19 +409,7 @@ __device__ __forceinline__ void emit(const Sink &sk, int64_t e, double n, double
 }
 
 // ------------------------------------------------------------------ cols --
-// blockIdx.x, with the blocks the hardware deals to one XCD (every 8th)
-// remapped to consecutive indices (a bijection of the grid):
-// each XCD then reads one contiguous range of every row
-// (the rows kernel's rotated start, rows_block, does not help the columns:
-// -0.1...-0.6% on the 64 GiB target / C4 / C2 column statistics,
-// profiles/r05zf_ab_colskew.log)
-__device__ __forceinline__ uint64_t xcd_block() {
-  uint64_t bid = blockIdx.x;
-  const uint64_t g8 = gridDim.x / 8 * 8;
-  if (bid < g8) bid = (bid % 8) * (g8 / 8) + bid / 8;
-  return bid;
-}
-
+// (the XCD-aware block order, xcd_block, is in bm_wave.h)
 struct ColsDesc {
   int64_t O, R, I;
   int64_t rchunk;
@@ -1165,17 +1153,6 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // ------------------------------------------------------------------ host --
-int dtype_size(int dt) {
-  switch (dt) {
-    case BM_BOOL: case BM_U8: case BM_I8: return 1;
-    case BM_U16: case BM_I16: case BM_F16: return 2;
-    case BM_U32: case BM_I32: case BM_F32: return 4;
-    case BM_U64: case BM_I64: case BM_F64: return 8;
-    default: return 0;
-  }
-}
-bool is_float(int dt) { return dt == BM_F16 || dt == BM_F32 || dt == BM_F64; }
-
 int mode_of(int stat, int dt) {
   if (stat == BM_STAT_MEAN) return M_MEAN;
   if (stat == BM_STAT_VAR || stat == BM_STAT_STD) return M_MOM;
@@ -1216,17 +1193,12 @@ struct RedPlan {
   int64_t ntc;
 };
 
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 RedPlan plan_reduce(int dt, int64_t O, int64_t R, int64_t I, const void *src, int64_t P) {
   RedPlan p{};
   const int es = dtype_size(dt);
-  const bool al16 = src == nullptr || ((uintptr_t)src % 16) == 0;
   if (I == 1) {
     p.rows = true;
-    int vec = 16 / es;
-    while (vec > 1 && !(R % vec == 0 && P % vec == 0 && (src == nullptr || ((uintptr_t)src % (vec * es)) == 0)))
-      vec >>= 1;
+    const int vec = pick_vec(16 / es, {R, P}, {{src, es}});
     p.vec = vec;
     const int64_t target_waves = 8192;
     int64_t nch = 1;
@@ -1244,9 +1216,7 @@ RedPlan plan_reduce(int dt, int64_t O, int64_t R, int64_t I, const void *src, in
     p.nchunks = cdiv(R, rc);
   } else {
     p.rows = false;
-    int vec = std::min(16 / es, 8);
-    (void)al16;
-    while (vec > 1 && !(I % vec == 0 && (src == nullptr || ((uintptr_t)src % (vec * es)) == 0))) vec >>= 1;
+    const int vec = pick_vec(std::min(16 / es, 8), {I}, {{src, es}});
     p.vec = vec;
     const int64_t ncolv = cdiv(I, vec);
     int tcv = 1;
@@ -1274,48 +1244,32 @@ RedPlan plan_reduce(int dt, int64_t O, int64_t R, int64_t I, const void *src, in
   return p;
 }
 
-// exact integer var / std: the same grids as the float kernels
-template <typename T>
-int launch_int_mom(const RedPlan &p, const T *s, int64_t O, int64_t R, int64_t P, int64_t I, Sink sk,
-                   hipStream_t st) {
+// The launches of a plan, written once for every kernel family: the rows or
+// columns descriptor filled, the grid split at the launch limit, and the
+// plan's vector width as a template argument.  rows(v, blocks, desc) and
+// cols(v, grid, desc) launch the one kernel of that width.
+template <typename T, typename FR, typename FC>
+void launch_plan(const RedPlan &p, int64_t O, int64_t R, int64_t P, int64_t I, FR &&rows, FC &&cols) {
   if (p.rows) {
     RowsDesc d;
     d.O = O; d.R = R; d.P = P; d.rchunk = p.rchunk;
     d.nchunks = make_fastdiv((uint64_t)p.nchunks);
     d.nitems = O * p.nchunks;
-    const int64_t blocks = cdiv(d.nitems, kThreads / 64);
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxBlocks) {
-      const int g = (int)std::min<int64_t>(kMaxBlocks, blocks - b0);
+    for_block_runs(cdiv(d.nitems, kThreads / 64), kThreads, [&](int64_t b0, int g) {
       d.item0 = b0 * (kThreads / 64);
-      switch (p.vec) {
-        case 16: if constexpr (sizeof(T) == 1) { k_red_rows_int<T, 16><<<g, kThreads, 0, st>>>(s, d, sk); } break;
-        case 8: k_red_rows_int<T, 8><<<g, kThreads, 0, st>>>(s, d, sk); break;
-        case 4: k_red_rows_int<T, 4><<<g, kThreads, 0, st>>>(s, d, sk); break;
-        case 2: k_red_rows_int<T, 2><<<g, kThreads, 0, st>>>(s, d, sk); break;
-        default: k_red_rows_int<T, 1><<<g, kThreads, 0, st>>>(s, d, sk); break;
-      }
-    }
-    return BM_OK;
+      for_vec<T, 16>(p.vec, [&](auto v) { rows(v, g, d); });
+    });
+  } else {
+    ColsDesc d;
+    d.O = O; d.R = R; d.I = I;
+    d.rchunk = p.rchunk; d.nchunks = p.nchunks;
+    d.tcv = p.tcv; d.nph = p.nph;
+    d.ntc = make_fastdiv((uint64_t)p.ntc);
+    for_tile_runs(O * p.ntc, p.nchunks, kThreads, [&](int64_t t0, dim3 grid) {
+      d.tile0 = t0;
+      for_vec<T, 8>(p.vec, [&](auto v) { cols(v, grid, d); });
+    });
   }
-  ColsDesc d;
-  d.O = O; d.R = R; d.I = I;
-  d.rchunk = p.rchunk; d.nchunks = p.nchunks;
-  d.tcv = p.tcv; d.nph = p.nph;
-  d.ntc = make_fastdiv((uint64_t)p.ntc);
-  const int64_t bx = O * p.ntc;
-  const int64_t per = std::max<int64_t>(1, kMaxBlocks / p.nchunks);
-  for (int64_t t0 = 0; t0 < bx; t0 += per) {
-    d.tile0 = t0;
-    dim3 grid((unsigned)std::min<int64_t>(per, bx - t0), (unsigned)p.nchunks);
-    const size_t lds = p.nph > 1 ? 2 * (size_t)kThreads * p.vec * sizeof(uint64_t) : 0;
-    switch (p.vec) {
-      case 8: k_red_cols_int<T, 8><<<grid, kThreads, lds, st>>>(s, d, sk); break;
-      case 4: k_red_cols_int<T, 4><<<grid, kThreads, lds, st>>>(s, d, sk); break;
-      case 2: k_red_cols_int<T, 2><<<grid, kThreads, lds, st>>>(s, d, sk); break;
-      default: k_red_cols_int<T, 1><<<grid, kThreads, lds, st>>>(s, d, sk); break;
-    }
-  }
-  return BM_OK;
 }
 
 // dynamic LDS of a k_red_cols launch: the row-phase buffers when nph > 1
@@ -1325,77 +1279,48 @@ template <int MODE> size_t cols_lds_bytes(int nph, int vec) {
 }
 
 template <typename T, int MODE>
-int launch_main_t(const RedPlan &p, const void *src, int64_t O, int64_t R, int64_t P, int64_t I, Sink sk,
-                  hipStream_t st) {
+void launch_main_t(const RedPlan &p, const void *src, int64_t O, int64_t R, int64_t P, int64_t I, Sink sk,
+                   hipStream_t st) {
   const T *s = (const T *)src;
   if constexpr (MODE == M_MOM && small_int<T>()) {
-    return launch_int_mom<T>(p, s, O, R, P, I, sk, st);
+    // exact integer var / std: the same grids as the float kernels
+    launch_plan<T>(
+        p, O, R, P, I,
+        [&](auto v, int g, const RowsDesc &d) {
+          k_red_rows_int<T, decltype(v)::value><<<g, kThreads, 0, st>>>(s, d, sk);
+        },
+        [&](auto v, dim3 grid, const ColsDesc &d) {
+          constexpr int V = decltype(v)::value;
+          const size_t lds = p.nph > 1 ? 2 * (size_t)kThreads * V * sizeof(uint64_t) : 0;
+          k_red_cols_int<T, V><<<grid, kThreads, lds, st>>>(s, d, sk);
+        });
+    return;
   }
-  if (p.rows) {
-    RowsDesc d;
-    d.O = O; d.R = R; d.P = P; d.rchunk = p.rchunk;
-    d.nchunks = make_fastdiv((uint64_t)p.nchunks);
-    d.nitems = O * p.nchunks;
-    const int64_t blocks = cdiv(d.nitems, kThreads / 64);
-    // one launch per kMaxBlocks blocks (HIP: grid * block threads < 2^32)
-    for (int64_t b0 = 0; b0 < blocks; b0 += kMaxBlocks) {
-      const int g = (int)std::min<int64_t>(kMaxBlocks, blocks - b0);
-      d.item0 = b0 * (kThreads / 64);
-      switch (p.vec) {
-#define BM_ROWS_CASE(V) \
-  case V: if constexpr (V * sizeof(T) <= 16) { k_red_rows<T, V, MODE><<<g, kThreads, 0, st>>>(s, d, sk); } break;
-        BM_ROWS_CASE(16) BM_ROWS_CASE(8) BM_ROWS_CASE(4) BM_ROWS_CASE(2)
-        default: k_red_rows<T, 1, MODE><<<g, kThreads, 0, st>>>(s, d, sk); break;
-#undef BM_ROWS_CASE
-      }
-    }
-  } else {
-    ColsDesc d;
-    d.O = O; d.R = R; d.I = I;
-    d.rchunk = p.rchunk; d.nchunks = p.nchunks;
-    d.tcv = p.tcv; d.nph = p.nph;
-    d.ntc = make_fastdiv((uint64_t)p.ntc);
-    const int64_t bx = O * p.ntc;
-    const int64_t per = std::max<int64_t>(1, kMaxBlocks / p.nchunks);
-    for (int64_t t0 = 0; t0 < bx; t0 += per) {
-      d.tile0 = t0;
-      dim3 grid((unsigned)std::min<int64_t>(per, bx - t0), (unsigned)p.nchunks);
-      switch (p.vec) {
-#define BM_COLS_CASE(V) \
-  case V: if constexpr (V * sizeof(T) <= 16) { k_red_cols<T, V, MODE><<<grid, kThreads, cols_lds_bytes<MODE>(p.nph, V), st>>>(s, d, sk); } break;
-        BM_COLS_CASE(8) BM_COLS_CASE(4) BM_COLS_CASE(2)
-        default: k_red_cols<T, 1, MODE><<<grid, kThreads, cols_lds_bytes<MODE>(p.nph, 1), st>>>(s, d, sk); break;
-#undef BM_COLS_CASE
-      }
-    }
-  }
-  return BM_OK;
+  // (no else: the library has always carried the M_MOM float kernels of the
+  // small integer types as well, and its set of kernels is left as it is)
+  launch_plan<T>(
+      p, O, R, P, I,
+      [&](auto v, int g, const RowsDesc &d) {
+        k_red_rows<T, decltype(v)::value, MODE><<<g, kThreads, 0, st>>>(s, d, sk);
+      },
+      [&](auto v, dim3 grid, const ColsDesc &d) {
+        constexpr int V = decltype(v)::value;
+        k_red_cols<T, V, MODE><<<grid, kThreads, cols_lds_bytes<MODE>(p.nph, V), st>>>(s, d, sk);
+      });
 }
 
 template <int MODE>
 int launch_main_m(int dt, const RedPlan &p, const void *src, int64_t O, int64_t R, int64_t P, int64_t I,
                   Sink sk, hipStream_t st) {
-  switch (dt) {
-    case BM_BOOL:
-    case BM_U8: return launch_main_t<uint8_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_I8: return launch_main_t<int8_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_U16: return launch_main_t<uint16_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_I16: return launch_main_t<int16_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_U32: return launch_main_t<uint32_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_I32: return launch_main_t<int32_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_U64: return launch_main_t<uint64_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_I64: return launch_main_t<int64_t, MODE>(p, src, O, R, P, I, sk, st);
-    case BM_F16:
-      if constexpr (!int_only_mode<MODE>()) return launch_main_t<_Float16, MODE>(p, src, O, R, P, I, sk, st);
-      break;
-    case BM_F32:
-      if constexpr (!int_only_mode<MODE>()) return launch_main_t<float, MODE>(p, src, O, R, P, I, sk, st);
-      break;
-    case BM_F64:
-      if constexpr (!int_only_mode<MODE>()) return launch_main_t<double, MODE>(p, src, O, R, P, I, sk, st);
-      break;
-    default: break;
-  }
+  bool done = false;
+  for_dtype(dt, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if constexpr (!(int_only_mode<MODE>() && is_float_t<T>())) {
+      launch_main_t<T, MODE>(p, src, O, R, P, I, sk, st);
+      done = true;
+    }
+  });
+  if (done) return BM_OK;
   bm_set_error("bm_reduce: unsupported dtype %d for this statistic", dt);
   return BM_E_ARG;
 }
@@ -1424,14 +1349,15 @@ int launch_main(int mode, int dt, const RedPlan &p, const void *src, int64_t O, 
 // bm_reduce_keep(BM_STAT_MEAN): the dual kernels, float inputs only
 int launch_keep_mean(int dt, const RedPlan &p, const void *src, int64_t O, int64_t R, int64_t P, int64_t I,
                      Sink sk, hipStream_t st) {
-  switch (dt) {
-    case BM_F16: return launch_main_t<_Float16, M_MEANMOM>(p, src, O, R, P, I, sk, st);
-    case BM_F32: return launch_main_t<float, M_MEANMOM>(p, src, O, R, P, I, sk, st);
-    case BM_F64: return launch_main_t<double, M_MEANMOM>(p, src, O, R, P, I, sk, st);
-    default: break;
+  if (!is_float(dt)) {
+    bm_set_error("bm_reduce_keep: dtype %d is not a float dtype", dt);
+    return BM_E_ARG;
   }
-  bm_set_error("bm_reduce_keep: dtype %d is not a float dtype", dt);
-  return BM_E_ARG;
+  for_dtype(dt, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if constexpr (is_float_t<T>()) launch_main_t<T, M_MEANMOM>(p, src, O, R, P, I, sk, st);
+  });
+  return BM_OK;
 }
 
 // block-per-output combine for few outputs from many parts
@@ -1448,19 +1374,9 @@ void launch_combine_k(int g, const double *p0, const double *p1, const CombDesc 
 template <int MODE>
 void launch_combine_m(int dt, int g, const double *p0, const double *p1, const CombDesc &cd, Sink sk,
                       hipStream_t st) {
-  switch (dt) {  // only max/min look at the element type
-    case BM_BOOL: case BM_U8: launch_combine_k<MODE, uint8_t>(g, p0, p1, cd, sk, st); break;
-    case BM_I8: launch_combine_k<MODE, int8_t>(g, p0, p1, cd, sk, st); break;
-    case BM_U16: launch_combine_k<MODE, uint16_t>(g, p0, p1, cd, sk, st); break;
-    case BM_I16: launch_combine_k<MODE, int16_t>(g, p0, p1, cd, sk, st); break;
-    case BM_U32: launch_combine_k<MODE, uint32_t>(g, p0, p1, cd, sk, st); break;
-    case BM_I32: launch_combine_k<MODE, int32_t>(g, p0, p1, cd, sk, st); break;
-    case BM_U64: launch_combine_k<MODE, uint64_t>(g, p0, p1, cd, sk, st); break;
-    case BM_I64: launch_combine_k<MODE, int64_t>(g, p0, p1, cd, sk, st); break;
-    case BM_F16: launch_combine_k<MODE, _Float16>(g, p0, p1, cd, sk, st); break;
-    case BM_F32: launch_combine_k<MODE, float>(g, p0, p1, cd, sk, st); break;
-    default: launch_combine_k<MODE, double>(g, p0, p1, cd, sk, st); break;
-  }
+  for_dtype(dt, [&](auto t) {  // only max/min look at the element type
+    launch_combine_k<MODE, typename decltype(t)::type>(g, p0, p1, cd, sk, st);
+  });
 }
 
 int launch_combine(int mode, int dt, const double *p0, const double *p1, const CombDesc &cd, Sink sk,
@@ -1497,15 +1413,6 @@ int check_args(int stat, int dt, int64_t O, int64_t R, int64_t I, const char *wh
     bm_set_error("%s: empty reduction (O=%lld R=%lld I=%lld)", who, (long long)O, (long long)R,
                  (long long)I);
     return BM_E_ARG;
-  }
-  return BM_OK;
-}
-
-int check_launch(const char *who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return BM_E_HIP;
   }
   return BM_OK;
 }

@@ -24,6 +24,7 @@
 //   centres to exact zeros (d is x - x) and its z-score is 0/0 = nan, as numpy
 //   gives; a nan in a row reaches its mean and so every output of the row.
 #include "bm_common.h"
+#include "bm_host.h"
 #include "bm_wave.h"
 #include "../../include/bolt_mi355x.h"
 
@@ -33,7 +34,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int64_t kMaxBlocks = 0xffffffffLL / kThreads;  // HIP launch limit: grid * block threads < 2^32
 // Plan of bm_standardize_rows.  All three thresholds are UNMEASURED: they are
 // set from the register budget, not from A/B runs.
 //   a thread holds lane_vecs(vec) = min(8, 32 / vec) vectors, that is
@@ -58,17 +58,6 @@ constexpr bool kRecip = false;
 #endif
 constexpr int kMaxVec = 8;  // elements per vector at most (1-byte inputs: 8-B loads, 64 B of float64 out)
 
-int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-int dtype_size(int dt) {
-  switch (dt) {
-    case BM_BOOL: case BM_U8: case BM_I8: return 1;
-    case BM_U16: case BM_I16: case BM_F16: return 2;
-    case BM_U32: case BM_I32: case BM_F32: return 4;
-    case BM_U64: case BM_I64: case BM_F64: return 8;
-    default: return 0;
-  }
-}
 // the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
 int stat_dtype(int dt) { return dt == BM_F16 || dt == BM_F32 ? dt : BM_F64; }
 
@@ -260,27 +249,21 @@ __global__ void __launch_bounds__(kThreads)
 // the widest vector (elements, a power of two) that every row start and both
 // pointers allow: n (the vectorised extent) and both pitches in whole
 // vectors, src aligned to its vector, dst to its stores of at most 16 B
-int pick_vec(int ies, int oes, int64_t n, int64_t sp, int64_t dp, const void *src, const void *dst) {
-  int vec = std::min(16 / ies, kMaxVec);
-  while (vec > 1 && !(n % vec == 0 && sp % vec == 0 && dp % vec == 0 && (uintptr_t)src % (size_t)(vec * ies) == 0 &&
-                      (uintptr_t)dst % (size_t)std::min(16, vec * oes) == 0))
-    vec >>= 1;
-  return vec;
+int std_vec(int ies, int oes, int64_t n, int64_t sp, int64_t dp, const void *src, const void *dst) {
+  return pick_vec(std::min(16 / ies, kMaxVec), {n, sp, dp}, {{src, ies}, {dst, oes}});
 }
 
 template <typename T, int VEC>
 void launch_rows_v(bool block, const void *src, void *dst, RowsArgs a, hipStream_t st) {
   typedef typename OutOf<T>::t OT;
   const int rpb = block ? 1 : kThreads / 64;
-  const int64_t blocks = cdiv(a.O, rpb);
-  for (int64_t b0 = 0; b0 < blocks; b0 += kMaxBlocks) {
-    const int g = (int)std::min<int64_t>(kMaxBlocks, blocks - b0);
+  for_block_runs(cdiv(a.O, rpb), kThreads, [&](int64_t b0, int g) {
     a.row0 = b0 * rpb;
     if (block)
       k_std_rows<T, VEC, lane_vecs(VEC), kThreads / 64><<<g, kThreads, 0, st>>>((const T *)src, (OT *)dst, a);
     else
       k_std_rows<T, VEC, lane_vecs(VEC), 1><<<g, kThreads, 0, st>>>((const T *)src, (OT *)dst, a);
-  }
+  });
 }
 
 template <typename T, int VEC>
@@ -295,49 +278,22 @@ void launch_apply_v(bool rows, const void *src, void *dst, const double *mean, c
     k_std_apply<T, VEC, false><<<g, kThreads, 0, st>>>((const T *)src, (OT *)dst, mean, sd, a);
 }
 
-// F<T, VEC>(args) for the runtime vec; vec * sizeof(T) <= 16 by pick_vec
-#define BM_STD_VEC(F, ...)                                                  \
-  switch (vec) {                                                            \
-    case 8: if constexpr (8 * sizeof(T) <= 16) { F<T, 8>(__VA_ARGS__); } break; \
-    case 4: if constexpr (4 * sizeof(T) <= 16) { F<T, 4>(__VA_ARGS__); } break; \
-    case 2: if constexpr (2 * sizeof(T) <= 16) { F<T, 2>(__VA_ARGS__); } break; \
-    default: F<T, 1>(__VA_ARGS__); break;                                   \
-  }
-template <typename T>
-void launch_rows_t(int vec, bool block, const void *src, void *dst, const RowsArgs &a, hipStream_t st) {
-  BM_STD_VEC(launch_rows_v, block, src, dst, a, st)
-}
-template <typename T>
-void launch_apply_t(int vec, bool rows, const void *src, void *dst, const double *mean, const double *sd,
-                    const ApplyArgs &a, hipStream_t st) {
-  BM_STD_VEC(launch_apply_v, rows, src, dst, mean, sd, a, st)
-}
-#undef BM_STD_VEC
-
-// F<T>(args) for the runtime dtype (bool through the uint8 kernels: its values are 0 / 1)
-#define BM_STD_DTYPE(F, ...)                                 \
-  switch (dt) {                                              \
-    case BM_BOOL:                                            \
-    case BM_U8: F<uint8_t>(__VA_ARGS__); break;              \
-    case BM_I8: F<int8_t>(__VA_ARGS__); break;               \
-    case BM_U16: F<uint16_t>(__VA_ARGS__); break;            \
-    case BM_I16: F<int16_t>(__VA_ARGS__); break;             \
-    case BM_U32: F<uint32_t>(__VA_ARGS__); break;            \
-    case BM_I32: F<int32_t>(__VA_ARGS__); break;             \
-    case BM_U64: F<uint64_t>(__VA_ARGS__); break;            \
-    case BM_I64: F<int64_t>(__VA_ARGS__); break;             \
-    case BM_F16: F<_Float16>(__VA_ARGS__); break;            \
-    case BM_F32: F<float>(__VA_ARGS__); break;               \
-    default: F<double>(__VA_ARGS__); break;                  \
-  }
+// the kernels of the runtime dtype (checked by check_dtypes) and vec (std_vec's)
 void launch_rows(int dt, int vec, bool block, const void *src, void *dst, const RowsArgs &a, hipStream_t st) {
-  BM_STD_DTYPE(launch_rows_t, vec, block, src, dst, a, st)
+  for_dtype(dt, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    for_vec<T, kMaxVec>(vec, [&](auto v) { launch_rows_v<T, decltype(v)::value>(block, src, dst, a, st); });
+  });
 }
 void launch_apply(int dt, int vec, bool rows, const void *src, void *dst, const double *mean, const double *sd,
                   const ApplyArgs &a, hipStream_t st) {
-  BM_STD_DTYPE(launch_apply_t, vec, rows, src, dst, mean, sd, a, st)
+  for_dtype(dt, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    for_vec<T, kMaxVec>(vec, [&](auto v) {
+      launch_apply_v<T, decltype(v)::value>(rows, src, dst, mean, sd, a, st);
+    });
+  });
 }
-#undef BM_STD_DTYPE
 
 int check_dtypes(const char *who, int in_dtype, int out_dtype) {
   if (dtype_size(in_dtype) == 0) {
@@ -348,15 +304,6 @@ int check_dtypes(const char *who, int in_dtype, int out_dtype) {
     bm_set_error("%s: out_dtype %d is not the statistics dtype %d of dtype %d (float16 / float32 keep "
                  "theirs, every other dtype gives float64)", who, out_dtype, stat_dtype(in_dtype), in_dtype);
     return BM_E_ARG;
-  }
-  return BM_OK;
-}
-
-int check_launch(const char *who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    bm_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
-    return BM_E_HIP;
   }
   return BM_OK;
 }
@@ -383,7 +330,7 @@ extern "C" int bm_standardize_rows(const void *src, int in_dtype, int64_t O, int
   *taken = 1;
   if (O == 0 || R == 0) return BM_OK;  // nothing to write
   const int ies = dtype_size(in_dtype), oes = dtype_size(out_dtype);
-  const int vec = pick_vec(ies, oes, R, src_pitch, dst_pitch, src, dst);
+  const int vec = std_vec(ies, oes, R, src_pitch, dst_pitch, src, dst);
   const int64_t held = (int64_t)vec * lane_vecs(vec);  // elements a thread holds
   const bool wave = R <= 64 * held;
   if (!wave && (R > kThreads * held || O < kBlockMinRows)) {
@@ -415,7 +362,7 @@ extern "C" int bm_standardize_apply(const void *src, int in_dtype, int64_t O, in
   if (O == 0 || R == 0 || I == 0) return BM_OK;  // nothing to write
   const int ies = dtype_size(in_dtype), oes = dtype_size(out_dtype);
   const bool rows = I == 1;
-  const int vec = rows ? pick_vec(ies, oes, R, src_pitch, dst_pitch, src, dst) : pick_vec(ies, oes, I, 0, 0, src, dst);
+  const int vec = rows ? std_vec(ies, oes, R, src_pitch, dst_pitch, src, dst) : std_vec(ies, oes, I, 0, 0, src, dst);
   ApplyArgs a{};
   a.R = R; a.I = I; a.sp = src_pitch; a.dp = dst_pitch;
   const int64_t nv = (rows ? R : I) / vec;

@@ -1,6 +1,8 @@
-// bm_wave.h -- wave-level helpers shared by the row kernels of bm_reduce.hip
-// and bm_standardize.hip (gfx950 only): the float64 element conversion, the
-// deterministic DPP fold of the 64 lanes and the XCD-aware block order.
+// bm_wave.h -- device helpers shared by the kernels of bm_reduce.hip,
+// bm_standardize.hip and bm_comoment.hip (gfx950 only): the float64 element
+// conversion, the deterministic DPP fold of the 64 lanes and the XCD-aware
+// block orders of the row kernels (rows_block) and the column kernels
+// (xcd_block).  Their host-side counterpart is bm_host.h.
 #pragma once
 
 #include "bm_common.h"
@@ -81,5 +83,20 @@ __device__ __forceinline__ uint64_t rows_block() {
     const uint64_t E = g8 / 8;
     bid = (bid % 8) * E + (bid / 8 + (bid % 8) * kRedXcdSkew) % E;
   }
+  return bid;
+}
+
+// ---- block order of the column kernels ----
+// blockIdx.x, with the blocks the hardware deals to one XCD (every 8th)
+// remapped to consecutive indices (a bijection of the grid): each XCD then
+// reads one contiguous range of every row, its blocks taking consecutive
+// column tiles (C4 var +1.1%, 64 GiB-target-shaped mean / std over axis 0
+// +2.2% / +1.6%, profiles/r05h_ab_cols_xcd.log).  The rows kernel's rotated
+// start (rows_block) does not help the columns: -0.1...-0.6% on the 64 GiB
+// target / C4 / C2 column statistics, profiles/r05zf_ab_colskew.log
+__device__ __forceinline__ uint64_t xcd_block() {
+  uint64_t bid = blockIdx.x;
+  const uint64_t g8 = gridDim.x / 8 * 8;
+  if (bid < g8) bid = (bid % 8) * (g8 / 8) + bid / 8;
   return bid;
 }
