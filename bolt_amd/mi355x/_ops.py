@@ -461,6 +461,43 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_comoment_combine")
 
+    def quantile_rows(self, src, code, O, R, pitch, ranks, frac, out, out_code):
+        """The quantiles (``ranks`` / ``frac``: see bm_quantile_rows) of O rows
+        of R elements, ``pitch`` elements apart, into ``out``: len(ranks)
+        planes of O values, from one read -> True if the rows were taken,
+        False (nothing launched) when they do not fit the registers
+        (quantile_select serves those)."""
+        taken = ctypes.c_int(0)
+        rc = self.lib.bm_quantile_rows(src.data_ptr(), code, O, R, pitch, _lib.i64_array(ranks),
+                                       _lib.f64_array(frac), len(ranks), out.data_ptr(), out_code,
+                                       ctypes.byref(taken), raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_quantile_rows")
+        return bool(taken.value)
+
+    def quantile_select(self, src, code, O, R, pitch, ranks, frac, out, out_code, workspace=None):
+        """quantile_rows for rows of any length: the streaming radix select
+        (bm_quantile_select).  ``workspace``: a tensor to use instead of one of
+        bm_quantile_workspace_bytes."""
+        import torch
+        if workspace is None:
+            S = len(ranks) + sum(1 for f in frac if f != 0.0)
+            key = ("quantile", code, O, R, S)
+            nws = self._ws.get(key)
+            if nws is None:
+                n = ctypes.c_size_t(0)
+                _lib.check(self.lib.bm_quantile_workspace_bytes(code, O, R, S, ctypes.byref(n)),
+                           "bm_quantile_workspace_bytes")
+                nws = self._ws[key] = n.value
+            workspace = torch.empty(nws, dtype=torch.uint8, device=src.device) if nws else None
+        nws = workspace.numel() if workspace is not None else 0
+        rc = self.lib.bm_quantile_select(src.data_ptr(), code, O, R, pitch, _lib.i64_array(ranks),
+                                         _lib.f64_array(frac), len(ranks), out.data_ptr(), out_code,
+                                         workspace.data_ptr() if workspace is not None else None, nws,
+                                         raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_quantile_select")
+
     def state_bytes(self, stat, code, nout):
         n = ctypes.c_size_t(0)
         _lib.check(self.lib.bm_reduce_state_bytes(stat, code, nout, ctypes.byref(n)), "bm_reduce_state_bytes")

@@ -21,6 +21,10 @@ Operations and what replaces the Spark machinery:
       deviation] along an axis, a device array of the same shape: rows over
       the last axis in one read and one write (bm_standardize_rows), other
       axes as one moments read plus bm_standardize_apply.
+  quantile / percentile / median: exact order statistics of every record
+      along an axis, host results: rows over the last axis selected by rank
+      from one read (bm_quantile_rows; longer rows bm_quantile_select), other
+      axes permuted to rows first.
   toarray / tolocal: D2H (+ all_gather of the slabs).
 """
 import collections
@@ -1575,6 +1579,177 @@ class BoltArrayMI355X(BoltArray):
         numpy.corrcoef does.  A record or a signal of zero variance gives nan.
         An addition to the reference's API."""
         return self._comoment(y, axis, keepdims, _lib.CO_CORR)
+
+    def _quantile(self, q, axis, keepdims, method, scale, who):
+        """``who`` (quantile / percentile / median) of every record over
+        ``axis`` at ``q`` / ``scale`` -> host result.
+
+        Planned with reduction.plan_for / plan.reduce_layout like _comoment,
+        and what it costs, per batch of quantiles (_lib.QUANTILE_MAX_RANKS
+        ranks: eight 'lower' / 'higher' quantiles, four 'linear' ones, each of
+        which needs two ranks):
+          * the last axis (rows dense or row-padded, read in place at their
+            pitch): one read of the array (bm_quantile_rows) for rows the
+            registers hold, else sizeof(element) reads (bm_quantile_select);
+          * every other layout -- columns, reduced axes that are not one
+            block, a padded array over other axes than the last -- is first
+            permuted into a dense temporary with the kept axes first, in
+            ascending order, and the reduced axes last (one bm_permute, or
+            one strided copy out of padded rows: one more read and write,
+            once for all batches), then runs as rows;
+          * across ranks, the sharded axis kept: every rank finishes its
+            slab's outputs and they are gathered (reduction.finish);
+          * across ranks, the sharded axis reduced with other axes kept: one
+            exchange (permute_sharded) brings the kept axes to the front, so
+            every rank holds whole records, then as the case before;
+          * across ranks, every axis reduced: NotImplementedError.
+        Moment states (KEEP_MOMENTS, swap states) are neither used nor left;
+        nothing is cached."""
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        if method not in ('linear', 'lower', 'higher'):
+            raise ValueError("%s: method must be 'linear', 'lower' or 'higher', got %r" % (who, method))
+        try:
+            qs = np.asarray(q)
+        except Exception:
+            raise ValueError("%s: q is not array-like" % who)
+        if qs.dtype.kind not in "biuf" or qs.ndim > 1 or (qs.ndim == 1 and qs.size == 0):
+            raise ValueError("%s: q must be a real scalar or a 1-D sequence of at least one, got dtype %s, shape %s"
+                             % (who, qs.dtype, qs.shape))
+        one = qs.ndim == 0
+        qs = qs.astype(np.float64).reshape(-1)
+        if not (np.isfinite(qs).all() and (qs >= 0).all() and (qs <= scale).all()):
+            raise ValueError("%s: q must be finite and in [0, %g], got %s" % (who, scale, qs))
+        if scale != 1:
+            qs = qs / scale
+        axes = tuple(sorted(set(int(a) for a in ax)))
+        n = self._nrecords(ax)
+        if n == 0 and method != 'linear':
+            raise ValueError("%s: method %r of no records" % (who, method))
+        world = self._ctx.world_size
+        if world > 1 and 0 in axes and len(axes) == self.ndim:
+            raise NotImplementedError("%s over every axis of an array sharded across %d ranks needs a distributed "
+                                      "select; reduce the sharded axis together with fewer axes" % (who, world))
+        plan, out_dtype, ocode = reduction.plan_for(self, ax, reduction.QUANTILE)
+        if method != 'linear':
+            out_dtype, ocode = self._dtype, plan.code   # one of the record's own values
+        K = len(qs)
+        if n == 0:
+            planes = [np.full(plan.out_shape, np.nan, dtype=out_dtype) for _ in range(K)]
+        else:
+            # pos = q (n - 1) in float64: lo / hi the floor(pos)-th / ceil(pos)-th smallest, g the rest
+            pos = qs * (n - 1)
+            fl = np.floor(pos)
+            if method == 'higher':
+                ranks, frac = np.ceil(pos).astype(np.int64).tolist(), [0.0] * K
+            elif method == 'lower':
+                ranks, frac = fl.astype(np.int64).tolist(), [0.0] * K
+            else:
+                ranks, frac = fl.astype(np.int64).tolist(), (pos - fl).tolist()
+            planes = self._quantile_planes(plan, out_dtype, ocode, ranks, frac)
+        vs = self._aligned_vshape(ax)
+        res = []
+        for arr in planes:
+            if vs is not None:
+                arr = arr.reshape(vs)
+            if keepdims:
+                for i in ax:
+                    arr = np.expand_dims(arr, axis=i)
+            res.append(arr)
+        arr = res[0] if one else np.stack(res)
+        if arr.ndim == 0:
+            arr = arr[()]
+        return BoltArrayLocal(arr).toscalar()
+
+    def _quantile_planes(self, plan, out_dtype, ocode, ranks, frac):
+        """_quantile's device work -> list of len(ranks) host arrays of
+        plan.out_shape.  The rows are laid out once; the quantiles run in
+        batches of at most _lib.QUANTILE_MAX_RANKS ranks."""
+        ctx, es = self._ctx, self._dtype.itemsize
+        d = self.__dict__
+        if plan.world > 1 and 0 in plan.axes:
+            # the sharded axis is reduced: the kept axes to the front across
+            # ranks (one exchange, as _tree_reduce's), whole records per rank
+            kept = [i for i in range(self.ndim) if i not in plan.axes]
+            gperm = kept + list(plan.axes)
+            pbuf = d.get("_pbuf")
+            data = permute_sharded(ctx, self._backend, pbuf if pbuf is not None else d["_data"], self._shape, gperm,
+                                   es, src_pitch=d.get("_pitch") if pbuf is not None else None)
+            tmp = self._like(data, tuple(self._shape[p] for p in gperm), len(kept))
+            tplan, _, _ = reduction.plan_for(tmp, tuple(range(len(kept), self.ndim)), reduction.QUANTILE)
+            return tmp._quantile_planes(tplan, out_dtype, ocode, ranks, frac)
+        lshape, nloc = plan.lshape, plan.nloc
+        R = int(np.prod([lshape[a] for a in plan.axes], dtype=np.int64))
+        O = nloc // R if R else 0
+        pbuf = d.get("_pbuf")
+        dev = self._device
+        be = backend_for(dev)
+        if plan.perm is None and plan.I == 1 and plan.R == R and (pbuf is None or R == lshape[-1]):
+            # the reduced axes are the rows: read in place, dense or a pitch apart
+            buf, pitch = (pbuf, d["_pitch"]) if pbuf is not None else (d["_data"], R)
+        else:
+            kept = [i for i in range(len(lshape)) if i not in plan.axes]
+            perm = kept + list(plan.axes)
+            buf, pitch = _empty(nloc * es, dev), R
+            if nloc and pbuf is not None:
+                pstr = padded_strides(lshape, d["_pitch"])
+                pshape = [lshape[p] for p in perm]
+                be.copy_strided(pbuf, 0, buf, 0, pshape, [pstr[p] for p in perm], padded_strides(pshape, pshape[-1]),
+                                es)
+            elif nloc:
+                be.permute(d["_data"], lshape, perm, es, buf)
+        single = plan.world == 1
+        run = O and nloc
+        planes = []
+        k0 = 0
+        while k0 < len(ranks):
+            k1, S = k0, 0
+            while k1 < len(ranks) and S + (2 if frac[k1] != 0.0 else 1) <= _lib.QUANTILE_MAX_RANKS:
+                S += 2 if frac[k1] != 0.0 else 1
+                k1 += 1
+            Kb = k1 - k0
+            outs = reduction.outputs(be, dev, out_dtype, Kb, O, single and run and
+                                     Kb * O * out_dtype.itemsize <= reduction.HOST_RESULT_MAX)
+            if run:
+                reduction.quantile_rows(be, buf, self._dtype, plan.code, O, R, pitch, ranks[k0:k1], frac[k0:k1],
+                                        outs[2] if outs[2] is not None else outs[1], out_dtype, ocode)
+            planes += reduction.finish(outs, dev, plan, out_dtype, Kb, O, None, None if single else ctx)
+            k0 = k1
+        return planes
+
+    def quantile(self, q, axis=None, keepdims=False, method='linear'):
+        """The ``q``-quantile(s) of every record over ``axis`` (None: every
+        axis; taken as mean() takes it): exact order statistics.  ``q`` is a
+        real scalar or a 1-D sequence of K >= 1 values, each finite and in
+        [0, 1]; ``method`` is 'linear', 'lower' or 'higher'; anything else
+        raises ValueError before any device work.  With n values reduced per
+        output, pos = q (n - 1) in float64, lo / hi the floor(pos)-th /
+        ceil(pos)-th smallest values and g = pos - floor(pos):
+        'lower' / 'higher' return lo / hi in the array's dtype, bit for bit
+        numpy.quantile's; 'linear' returns lo where g == 0, else
+        lo + (hi - lo) g evaluated in float64 (three separately rounded
+        operations) and rounded once to the statistics dtype (float16 /
+        float32 keep theirs, every other dtype gives float64: numpy's result
+        dtypes).  int64 / uint64 values beyond 2^53 round when 'linear'
+        converts them to float64.  Floats order as IEEE values, -0.0 before
+        +0.0; a record holding a NaN gives NaN for every q and method; bool
+        runs as uint8.  No records: 'linear' gives nan, 'lower' / 'higher'
+        raise ValueError.  The result is a host result as cov() returns its
+        planes, of the kept axes' shape ((K,) + that for a sequence;
+        ``keepdims`` re-inserts the reduced axes after the K axis).  Over the
+        last axis the array is read once per four 'linear' (eight 'lower' /
+        'higher') quantiles; what other layouts cost: _quantile.  An addition
+        to the reference's API."""
+        return self._quantile(q, axis, keepdims, method, 1, "quantile")
+
+    def percentile(self, q, axis=None, keepdims=False, method='linear'):
+        """quantile(q / 100): ``q`` in [0, 100].  An addition to the reference's API."""
+        return self._quantile(q, axis, keepdims, method, 100, "percentile")
+
+    def median(self, axis=None, keepdims=False):
+        """quantile(0.5): the median of every record over ``axis``.  An
+        addition to the reference's API."""
+        return self._quantile(0.5, axis, keepdims, 'linear', 1, "median")
 
     def _stat(self, axis=None, func=None, name=None, keepdims=False):
         """Statistic over ``axis`` (array.py:284-334); results are host arrays / scalars."""

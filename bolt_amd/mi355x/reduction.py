@@ -1,7 +1,7 @@
 """Mechanics of the statistics: how the reduced axes of an array lie in HBM and
 what is launched to reduce over them.  One plan, one source, one finish, for
 array.py's _reduced (one statistic), _reduced_moments (stats()),
-_standardized (center / zscore) and _comoment (cov / corr).  The rules -- what is kept, padded or fused,
+_standardized (center / zscore), _comoment (cov / corr) and _quantile (quantile / percentile / median).  The rules -- what is kept, padded or fused,
 and their switches -- stay in array.py; this module never imports it and is
 handed the array.
 """
@@ -21,6 +21,7 @@ _KEEP_DTYPE = (_lib.STAT_SUM, _lib.STAT_MAX, _lib.STAT_MIN, _lib.STAT_PROD, _lib
                _lib.STAT_BOR, _lib.STAT_BXOR, _lib.STAT_FMAX, _lib.STAT_FMIN)
 STANDARDIZE = 'standardize'  # plan_for's statistic for center / zscore: the dtype of ``record - 0.0``
 COMOMENT = 'comoment'  # plan_for's statistic for cov / corr: the statistics dtype of the outputs
+QUANTILE = 'quantile'  # plan_for's statistic for an interpolated quantile: the dtype of ``record - 0.0``, as STANDARDIZE
 STATS_FIELDS = ('mean', 'var', 'std')  # the order of bm_reduce_moments' outputs
 
 # What reducing ``axes`` (sorted) of an array needs, from its shapes and dtype
@@ -42,7 +43,7 @@ _tuple_new = tuple.__new__
 
 def plan_for(arr, axis, stat):
     """-> (the Plan of reducing ``axis`` of ``arr``, the result dtype of
-    ``stat`` -- a _lib.STAT_*, STANDARDIZE or COMOMENT -- and its code)."""
+    ``stat`` -- a _lib.STAT_*, STANDARDIZE, COMOMENT or QUANTILE -- and its code)."""
     lshape = arr._local_shape
     key = (lshape, tuple(axis), arr._dtype, arr._shape, arr._ctx.world_size)
     plan = _PLANS.get(key)
@@ -63,7 +64,7 @@ def plan_for(arr, axis, stat):
         elif stat in (_lib.STAT_LAND, _lib.STAT_LOR):
             dt = np.dtype(bool)
         else:
-            dt = stat_dtype(plan.dtype, (1,) if stat == STANDARDIZE else plan.out_shape)
+            dt = stat_dtype(plan.dtype, (1,) if stat in (STANDARDIZE, QUANTILE) else plan.out_shape)
         out = plan.outs[stat] = (dt, dtype_code(dt))
     return plan, out[0], out[1]
 
@@ -376,6 +377,52 @@ def comoment_combine(be, what, states, counts, ymean, ym2, nout, K, out, out_dty
         r = torch.where(den > 0, torch.clamp(C / torch.sqrt(den), -1.0, 1.0),
                         torch.full_like(den, float("nan")))   # no variance, no correlation
     F.view(out, (K, nout), out_dtype).copy_(r.to(F.torch_dtype(out_dtype)))
+
+
+def quantile_rows(be, buf, dtype, code, O, R, pitch, ranks, frac, out, out_dtype, ocode):
+    """The quantiles of O rows of R elements, ``pitch`` elements apart in
+    ``buf``, into ``out``: len(ranks) planes of O values of ``out_dtype``.
+    Quantile k is the value lo of rank ranks[k] where frac[k] == 0, else
+    lo + (hi - lo) * frac[k] in float64 with hi the value of the next rank
+    (bm_quantile_rows; rows the registers do not hold: bm_quantile_select).  A
+    row holding a NaN gives NaN."""
+    if hasattr(be, "quantile_rows"):
+        if not be.quantile_rows(buf, code, O, R, pitch, ranks, frac, out, ocode):
+            be.quantile_select(buf, code, O, R, pitch, ranks, frac, out, ocode)
+        return
+    # an executor without the entry points (the CPU test executor): torch.sort
+    # of the rows, the same ranks, the same formula.  torch sorts no uint16 /
+    # uint32 / uint64: they are sorted as the signed type with the sign bit
+    # flipped, which keeps their order
+    import torch
+    from bolt_amd.mi355x import functional as F
+    dtype = np.dtype(dtype)
+    es = dtype.itemsize
+    sort_dt, flip = dtype, None
+    if dtype == np.bool_:
+        sort_dt = np.dtype(np.uint8)
+    elif dtype.kind == "u" and es > 1:
+        sort_dt = np.dtype("i%d" % es)
+        flip = -(1 << (8 * es - 1))
+    x = F.view(buf[:O * pitch * es], (O, pitch), sort_dt)[:, :R]
+    if flip is not None:
+        x = x ^ flip
+    srt = torch.sort(x, dim=1).values   # (NaNs last)
+    res = F.view(out, (len(ranks), O), out_dtype)
+    for k, (r, g) in enumerate(zip(ranks, frac)):
+        cols = srt[:, r:r + 2] if g != 0.0 else srt[:, r:r + 1]
+        if flip is not None:
+            cols = cols ^ flip
+        v = cols.contiguous().cpu().numpy().view(dtype)
+        if g == 0.0 and out_dtype == dtype:
+            val = v[:, 0]
+        else:
+            lo = v[:, 0].astype(np.float64)
+            with np.errstate(all="ignore"):
+                val = (lo + (v[:, 1].astype(np.float64) - lo) * g) if g != 0.0 else lo
+        if dtype.kind == "f":
+            val = np.where(torch.isnan(srt[:, R - 1]).cpu().numpy(), np.nan, val)
+        res[k] = torch.from_numpy(np.ascontiguousarray(val.astype(out_dtype))).to(res.device)
 
 
 def merge_equal_counts(planes, Rl, nrows):

@@ -505,6 +505,72 @@ int bm_comoment_combine(int what, const void *states, const int64_t *counts,
                         void *stream);
 
 /*
+ * quantile() / percentile() / median(): exact order statistics of rows.
+ * No reference call site: an API addition (the reference has no such method;
+ * its users sort every record on the host through map()).  An order statistic
+ * is one of the row's own values: both entry points select by rank on
+ * order-preserving unsigned keys of the element's width (floats in IEEE order,
+ * -0.0 before +0.0) and decode the selected key, so nothing is rounded but the
+ * interpolation.  A call takes nq quantiles, quantile k given as
+ *   ranks[k]: the 0-based rank of lo among the row's R values, and
+ *   frac[k] in [0, 1): 0 gives lo; otherwise lo + (hi - lo) * frac[k] with hi
+ *     the value of rank ranks[k] + 1, evaluated in float64 as three separately
+ *     rounded operations (no fused multiply-add) and rounded once to out_dtype.
+ * A quantile with frac != 0 takes two ranks; a call takes at most
+ * BM_QUANTILE_MAX_RANKS ranks.  out: nq planes of O values, plane k at
+ * out + k * O elements; it may be a bm_host_writable buffer.  out_dtype is
+ * in_dtype itself (every frac 0: the selected elements, bit for bit) or the
+ * statistics dtype of in_dtype (float16 / float32 keep theirs, every other
+ * dtype gives float64; 64-bit integers beyond 2^53 round when converted).  A
+ * row holding a NaN gives NaN in every output.  bool runs as uint8.
+ */
+#define BM_QUANTILE_MAX_RANKS 8
+
+/*
+ * bm_quantile_rows -- the quantiles of O rows of R elements, row_pitch >= R
+ * elements apart (the pad is never read), from one read: each row is held in
+ * registers as keys -- one wave per row, or one 256-thread block per longer
+ * row -- and every rank is found by a binary search over the key's bits,
+ * counting the keys below a candidate.  No reference call site: an API
+ * addition.  *taken = 1 when the planes were written; *taken = 0 and nothing
+ * launched when a row is longer than the kernels hold on chip, or when longer
+ * rows are too few to give each a block (bm_quantile_select serves those).
+ * O == 0 or R == 0 writes nothing (*taken = 1).  Arguments are checked before
+ * any launch: null pointers, a bad dtype, an out_dtype that is neither of the
+ * two above, negative extents, a pitch below R, nq outside 1..8, a frac
+ * outside [0, 1), a rank (+ 1 where frac != 0) that is not below R and more
+ * than BM_QUANTILE_MAX_RANKS ranks give BM_E_ARG.
+ */
+int bm_quantile_rows(const void *src, int in_dtype, int64_t O, int64_t R,
+                     int64_t row_pitch, const int64_t *ranks,
+                     const double *frac, int nq, void *out, int out_dtype,
+                     int *taken, void *stream);
+
+/*
+ * bm_quantile_workspace_bytes -- scratch bm_quantile_select needs for O rows
+ * and nranks ranks (nq plus one per frac != 0): the histograms, prefixes and
+ * NaN counts of one batch of rows.  No reference call site: an API addition.
+ * Monotone in O and nranks; O == 0 or R == 0 gives 0.
+ */
+int bm_quantile_workspace_bytes(int in_dtype, int64_t O, int64_t R, int nranks,
+                                size_t *bytes);
+
+/*
+ * bm_quantile_select -- bm_quantile_rows' result for rows of any length: a
+ * most-significant-byte-first radix select, sizeof(element) reads of the rows.
+ * Each pass adds the keys that match a rank's prefix to 256-bin histograms
+ * (LDS, then 64-bit integer atomics: deterministic) over rows x blocks per
+ * row, so that one long row still fills the device, and a pick kernel extends
+ * every prefix by the byte its rank falls in.  No reference call site: an API
+ * addition.  workspace: bm_quantile_workspace_bytes (BM_E_WS if smaller or
+ * NULL).  Arguments are checked as bm_quantile_rows checks them.
+ */
+int bm_quantile_select(const void *src, int in_dtype, int64_t O, int64_t R,
+                       int64_t row_pitch, const int64_t *ranks,
+                       const double *frac, int nq, void *out, int out_dtype,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * ---------------------------------------------------------------------------
  * Multi-GPU record exchange over RCCL (xGMI), one process per GPU.
  *
