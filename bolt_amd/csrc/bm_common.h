@@ -176,3 +176,10 @@ void bm_set_error(const char *fmt, ...);
 // state of bm_reduce_state (mean[nrows], M2[nrows]).
 int bm_merge_tile_moments(const double *parts, int64_t nparts, int64_t tb, int64_t R, int64_t nrows,
                           double *state, hipStream_t stream);
+
+// bm_standardize.hip, for bm_normalize_rows (bm_quantile.hip): bm_standardize_rows'
+// plan and launch behind the argument checks.  mode 0 / 1: its scale; 2:
+// (x - mean) / (mean + offset), the mean formed as for the other two.
+int bm_standardize_rows_checked(const char *who, const void *src, int in_dtype, int64_t O, int64_t R,
+                                int64_t src_pitch, void *dst, int out_dtype, int64_t dst_pitch, int mode,
+                                double offset, int *taken, hipStream_t stream);

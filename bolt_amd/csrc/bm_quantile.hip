@@ -44,6 +44,11 @@
 //   the rows kernel's epilogue and in k_q_finish.
 // Cost: one read of the array (rows), sizeof(element) reads (streaming), no
 //   write but the planes.
+// bm_normalize_rows (normalize(): (x - b) / (b + offset) against a percentile
+//   baseline b) lives here too: k_norm_rows is the rows kernel for one
+//   quantile with a second half -- the keys are invertible, so the held row
+//   is decoded, normalised in float64 and stored: one read, one write.  Its
+//   mean baseline is k_std_rows' (bm_standardize.hip), mode 2.
 #include "bm_common.h"
 #include "bm_host.h"
 #include "bm_wave.h"
@@ -240,6 +245,95 @@ template <int WPR> __device__ __forceinline__ uint64_t row_min(uint64_t x, int l
   }
 }
 
+// k_q_rows' three steps on a row held as keys -- the read, the bit search and
+// the step to the next rank -- as functions, for k_norm_rows.  k_q_rows keeps
+// its own text below: built from these functions its register allocation
+// changed (float32, 16-B vectors, wave per row: 103 VGPRs and four waves a SIMD
+// instead of 73 and six), and its measured times are not to move with an
+// addition.  WPR waves per row (1, or the block's 4), each thread holding NV
+// vectors of VEC elements: R <= 64 * WPR * VEC * NV (the host's plan),
+// R % VEC == 0.  K: the unsigned integer of the element's width.
+
+// the one read: thread slot j0, j < R leaves a whole vector inside the row
+// (R % VEC == 0).  nin: the thread's vectors inside the row, its first nin
+// (one register instead of k_q_rows' NV lane masks, which would stay live
+// across the search).  -> this thread saw a NaN
+template <typename K, int VEC, int NV, int WPR>
+__device__ __forceinline__ bool load_keys(const K *s, int64_t j0, int64_t R, const KeyMask &km,
+                                          typename Held<K>::t (&key)[NV][VEC], int &nin) {
+  typedef typename Held<K>::t HK;
+  constexpr int64_t stride = (int64_t)64 * WPR * VEC;
+  bool nan = false;
+  nin = 0;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+    const bool in = j0 + u * stride < R;
+    nin += in ? 1 : 0;
+    K v[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = K(0);
+    if (in) vload_nt<K, VEC>(s + j0 + u * stride, v);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      nan = nan || (in && is_nan_bits<K>(v[i], km.nan_above));
+      key[u][i] = in ? encode<K>(v[i], km) : (HK)(K)~K(0);
+    }
+  }
+  return nan;
+}
+
+// the key of rank `rank` among the row's keys: the binary search over the key's bits
+template <typename K, int VEC, int NV, int WPR>
+__device__ __forceinline__ typename Held<K>::t find_rank(const typename Held<K>::t (&key)[NV][VEC], uint32_t rank,
+                                                         int lane, int wave, uint32_t (*smc)[kWaves], int &par) {
+  typedef typename Held<K>::t HK;
+  constexpr int BITS = 8 * sizeof(K);
+  HK lo = 0;
+  for (int bit = BITS - 1; bit >= 0; --bit) {
+    const HK cand = lo | (HK(1) << bit);
+    uint32_t c = 0;
+    if constexpr (kLaneSum) {
+      uint32_t cl = 0;  // at most 32: six bits
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) cl += key[u][i] < cand ? 1u : 0u;
+      }
+#pragma unroll
+      for (int b = 0; b < 6; ++b) c += popc64(__builtin_amdgcn_ballot_w64((cl >> b & 1u) != 0)) << b;
+    } else {
+#pragma unroll
+      for (int u = 0; u < NV; ++u) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) c += popc64(__builtin_amdgcn_ballot_w64(key[u][i] < cand));
+      }
+    }
+    c = row_count<WPR>(c, lane, wave, smc, par);
+    if (c <= rank) lo = cand;
+  }
+  return lo;
+}
+
+// given the key lo of rank `rank`, the key of rank + 1 (rank + 1 < R: the caller's check)
+template <typename K, int VEC, int NV, int WPR>
+__device__ __forceinline__ uint64_t next_key(const typename Held<K>::t (&key)[NV][VEC], int nin,
+                                             typename Held<K>::t lo, uint32_t rank, int lane, int wave,
+                                             uint32_t (*smc)[kWaves], int &par, uint64_t *smk) {
+  uint32_t cle = 0;
+  uint64_t mn = ~0ull;
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      cle += popc64(__builtin_amdgcn_ballot_w64(u < nin && key[u][i] <= lo));
+      if (u < nin && key[u][i] > lo && (uint64_t)key[u][i] < mn) mn = key[u][i];
+    }
+  }
+  cle = row_count<WPR>(cle, lane, wave, smc, par);
+  mn = row_min<WPR>(mn, lane, wave, smk);
+  return cle <= rank + 1 ? mn : (uint64_t)lo;  // rank + 1 < R: a key above lo exists
+}
+
 // WPR waves per row (1, or the block's 4), each thread holding NV vectors of
 // VEC elements: R <= 64 * WPR * VEC * NV (the host's plan), R % VEC == 0.  K:
 // the unsigned integer of the element's width.
@@ -322,6 +416,111 @@ __global__ void __launch_bounds__(kThreads) k_q_rows(const K *__restrict__ src, 
       if (cle <= rank + 1) hi = mn;  // rank + 1 < R: a key above lo exists
     }
     if ((WPR == 1 ? lane : (int)threadIdx.x) == 0) emit(out, a.O, row, k, q, lo, hi, row_nan);
+  }
+}
+
+// ------------------------------------------------------------- normalize --
+// bm_normalize_rows' percentile baseline: k_q_rows' read and search for one
+// quantile, then the held keys are decoded back to the row's values,
+// normalised against the baseline and stored -- one read, one write.
+struct NormArgs {
+  int64_t O, R;
+  int64_t sp, dp;  // elements between row starts of src / dst (>= R)
+  int64_t row0;    // first row of this launch (launches split at the grid limit)
+  int64_t rank;    // as bm_quantile_rows' ranks[0] / frac[0]
+  double frac;
+  double offset;
+};
+
+// key_mask of the element type: a constant in k_norm_rows, which is built per
+// element type (its outputs are), where k_q_rows takes the masks as arguments
+template <typename T> __device__ constexpr KeyMask mask_of() {
+  constexpr int es = sizeof(T);
+  constexpr bool flt = std::is_same<T, _Float16>::value || std::is_floating_point<T>::value;
+  constexpr bool sgn = !flt && std::is_signed<T>::value;
+  constexpr uint64_t sign = 1ull << (8 * es - 1), all = ~0ull >> (64 - 8 * es);
+  return KeyMask{flt ? all : sgn ? sign : 0, flt || sgn ? sign : 0,
+                 !flt ? ~0ull : es == 2 ? 0x7C00ull : es == 4 ? 0x7F800000ull : 0x7FF0000000000000ull};
+}
+
+template <typename T> struct BitsOf {
+  typedef typename std::conditional<
+      sizeof(T) == 1, uint8_t,
+      typename std::conditional<sizeof(T) == 2, uint16_t,
+                                typename std::conditional<sizeof(T) == 4, uint32_t, uint64_t>::type>::type>::type t;
+};
+
+// the element a held key was made from, as float64 (encode's way back, then bits_f64's conversion)
+template <typename T> __device__ __forceinline__ double key_f64(typename Held<typename BitsOf<T>::t>::t key,
+                                                                const KeyMask &m) {
+  typedef typename BitsOf<T>::t K;
+  typedef typename Held<K>::t HK;
+  constexpr HK sign = HK(1) << (8 * sizeof(K) - 1);
+  const K b = (K)(key ^ ((key & sign) ? (HK)m.pos : (HK)m.neg));
+  return to_f64(__builtin_bit_cast(T, b));
+}
+
+// The baseline b is formed by every thread from the row-uniform keys lo / hi
+// (the counts and the minimum reach every wave of a block through LDS), in
+// float64 exactly as emit forms it.  x - b, b + offset and the division are
+// three separately rounded float64 operations (contraction is off in this
+// file), rounded once to the output type.  A row holding a NaN: b is NaN, and
+// so is every output.  The keys stay live until the last store; widening
+// outputs (float64 from 1-, 2- and 4-byte integers) leave as 16-B stores.
+template <typename T, int VEC, int NV, int WPR>
+__global__ void __launch_bounds__(kThreads)
+    k_norm_rows(const T *__restrict__ src, typename OutOf<T>::t *__restrict__ dst, NormArgs a) {
+  typedef typename OutOf<T>::t OT;
+  typedef typename BitsOf<T>::t K;
+  typedef typename Held<K>::t HK;
+  __shared__ uint32_t smc[2][kWaves];
+  __shared__ uint64_t smk[kWaves];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  constexpr int RPB = kThreads / 64 / WPR;  // rows per block
+  const int64_t row = a.row0 + (int64_t)rows_block() * RPB + (WPR == 1 ? wave : 0);
+  // wave per row: whole waves leave, and no barrier follows; block per row: the whole block leaves
+  if (row >= a.O) return;
+  constexpr int64_t stride = (int64_t)64 * WPR * VEC;
+  const int64_t j0 = (int64_t)(WPR == 1 ? lane : (int)threadIdx.x) * VEC;
+
+  // this thread's first output, formed before the search: a per-lane address
+  // lives in vector registers, of which the search leaves enough, where dst
+  // and its pitch would wait in scalar registers, of which it does not
+  OT *o = dst + row * a.dp + j0;
+  asm volatile("" : "+v"(o));  // (formed here, not re-formed at the stores)
+  constexpr KeyMask km = mask_of<T>();
+  HK key[NV][VEC];
+  int nin;
+  const bool nan = load_keys<K, VEC, NV, WPR>((const K *)src + row * a.sp, j0, a.R, km, key, nin);
+  int par = 0;
+  const bool row_nan = row_count<WPR>(popc64(__builtin_amdgcn_ballot_w64(nan)), lane, wave, smc, par) != 0;
+
+  const uint32_t rank = (uint32_t)a.rank;
+  const HK klo = find_rank<K, VEC, NV, WPR>(key, rank, lane, wave, smc, par);
+  const double lo = key_f64<T>(klo, km);
+  double b = lo;
+  if (a.frac != 0.0) {  // (uniform)
+    const HK khi = (HK)next_key<K, VEC, NV, WPR>(key, nin, klo, rank, lane, wave, smc, par, smk);
+    const double d = key_f64<T>(khi, km) - lo;  // three roundings, none fused
+    const double t = d * a.frac;
+    b = lo + t;
+  }
+  if (row_nan) b = __builtin_nan("");
+  const double den = b + a.offset;
+
+  // the one write
+#pragma unroll
+  for (int u = 0; u < NV; ++u) {
+    if (u < nin) {
+      OT ov[VEC];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const double d = key_f64<T>(key[u][i], km) - b;
+        ov[i] = (OT)(d / den);
+      }
+      store_out_nt<OT, VEC>(o + u * stride, ov);
+    }
   }
 }
 
@@ -458,6 +657,24 @@ int rows_vec(int es, int64_t R, int64_t P, const void *src) {
   return pick_vec(std::min(16 / es, kMaxVec), {R, P}, {{src, es}});
 }
 
+template <typename T, int VEC> void launch_norm_v(bool block, const void *src, void *dst, NormArgs a, hipStream_t st) {
+  typedef typename OutOf<T>::t OT;
+  const int rpb = block ? 1 : kThreads / 64;
+  for_block_runs(cdiv(a.O, rpb), kThreads, [&](int64_t b0, int g) {
+    a.row0 = b0 * rpb;
+    if (block)
+      k_norm_rows<T, VEC, lane_vecs(VEC), kWaves><<<g, kThreads, 0, st>>>((const T *)src, (OT *)dst, a);
+    else
+      k_norm_rows<T, VEC, lane_vecs(VEC), 1><<<g, kThreads, 0, st>>>((const T *)src, (OT *)dst, a);
+  });
+}
+
+// rows_vec where the rows are also written: the vector divides dst's pitch and
+// dst is aligned to its stores of at most 16 B (bm_standardize.hip's std_vec)
+int norm_vec(int ies, int oes, int64_t R, int64_t sp, int64_t dp, const void *src, const void *dst) {
+  return pick_vec(std::min(16 / ies, kMaxVec), {R, sp, dp}, {{src, ies}, {dst, oes}});
+}
+
 // the checks both entry points share; fills q (and the count of searched ranks)
 int check_spec(const char *who, const void *src, int in_dtype, int64_t O, int64_t R, int64_t pitch,
                const int64_t *ranks, const double *frac, int nq, const void *out, int out_dtype, QSpec *q, Search *sr) {
@@ -546,6 +763,61 @@ extern "C" int bm_quantile_rows(const void *src, int in_dtype, int64_t O, int64_
     for_vec<K, kMaxVec>(vec, [&](auto v) {
       launch_rows_v<K, decltype(v)::value>(!wave, src, out, a, q, (hipStream_t)stream);
     });
+  });
+  return check_launch(who);
+}
+
+extern "C" int bm_normalize_rows(const void *src, int in_dtype, int64_t O, int64_t R, int64_t src_pitch, int baseline,
+                                 int64_t rank, double frac, double offset, void *dst, int out_dtype,
+                                 int64_t dst_pitch, int *taken, void *stream) {
+  const char *who = "bm_normalize_rows";
+  if (!src || !dst || !taken) { bm_set_error("%s: null pointer", who); return BM_E_ARG; }
+  if (dtype_size(in_dtype) == 0) { bm_set_error("%s: bad dtype %d", who, in_dtype); return BM_E_ARG; }
+  if (out_dtype != stat_dtype(in_dtype)) {
+    bm_set_error("%s: out_dtype %d is not the statistics dtype %d of dtype %d (float16 / float32 keep "
+                 "theirs, every other dtype gives float64)", who, out_dtype, stat_dtype(in_dtype), in_dtype);
+    return BM_E_ARG;
+  }
+  if (O < 0 || R < 0) {
+    bm_set_error("%s: negative extent (O=%lld R=%lld)", who, (long long)O, (long long)R);
+    return BM_E_ARG;
+  }
+  if (src_pitch < R || dst_pitch < R) {
+    bm_set_error("%s: pitch below the row length (src_pitch=%lld dst_pitch=%lld R=%lld)", who,
+                 (long long)src_pitch, (long long)dst_pitch, (long long)R);
+    return BM_E_ARG;
+  }
+  if (baseline != BM_NORM_MEAN && baseline != BM_NORM_RANK) {
+    bm_set_error("%s: baseline %d is not BM_NORM_MEAN or BM_NORM_RANK", who, baseline);
+    return BM_E_ARG;
+  }
+  if (!std::isfinite(offset)) { bm_set_error("%s: offset %g is not finite", who, offset); return BM_E_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (baseline == BM_NORM_MEAN)
+    return bm_standardize_rows_checked(who, src, in_dtype, O, R, src_pitch, dst, out_dtype, dst_pitch, 2, offset,
+                                       taken, st);
+  const bool two = frac != 0.0;
+  if (!(frac >= 0.0 && frac < 1.0)) { bm_set_error("%s: frac=%g is not in [0, 1)", who, frac); return BM_E_ARG; }
+  if (rank < 0 || (O > 0 && R > 0 && rank + (two ? 1 : 0) >= R)) {
+    bm_set_error("%s: rank %lld%s is not below the row length R=%lld", who, (long long)rank,
+                 two ? " (+ 1: frac != 0)" : "", (long long)R);
+    return BM_E_ARG;
+  }
+  *taken = 1;
+  if (O == 0 || R == 0) return BM_OK;  // nothing to write
+  const int ies = dtype_size(in_dtype), oes = dtype_size(out_dtype);
+  const int vec = norm_vec(ies, oes, R, src_pitch, dst_pitch, src, dst);
+  const int64_t held = (int64_t)vec * lane_vecs(vec);  // elements a thread holds
+  const bool wave = R <= 64 * held;
+  if (!wave && (R > kThreads * held || O < kBlockMinRows)) {
+    *taken = 0;  // bm_quantile_rows' plan: the caller forms the baseline plane, then bm_standardize_apply
+    return BM_OK;
+  }
+  NormArgs a{};
+  a.O = O; a.R = R; a.sp = src_pitch; a.dp = dst_pitch; a.rank = rank; a.frac = frac; a.offset = offset;
+  for_dtype(in_dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    for_vec<T, kMaxVec>(vec, [&](auto v) { launch_norm_v<T, decltype(v)::value>(!wave, src, dst, a, st); });
   });
   return check_launch(who);
 }

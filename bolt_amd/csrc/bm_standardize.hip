@@ -23,6 +23,9 @@
 //   division) and rounded once to the output dtype.  A row of zero variance
 //   centres to exact zeros (d is x - x) and its z-score is 0/0 = nan, as numpy
 //   gives; a nan in a row reaches its mean and so every output of the row.
+// The rows kernel also serves bm_normalize_rows' mean baseline (bm_quantile.hip
+//   holds the entry point): mode 2 divides d by mean + offset instead of std,
+//   so the second pass over the held values is not run.
 #include "bm_common.h"
 #include "bm_host.h"
 #include "bm_wave.h"
@@ -61,32 +64,13 @@ constexpr int kMaxVec = 8;  // elements per vector at most (1-byte inputs: 8-B l
 // the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
 int stat_dtype(int dt) { return dt == BM_F16 || dt == BM_F32 ? dt : BM_F64; }
 
-template <typename T> struct OutOf { typedef double t; };
-template <> struct OutOf<_Float16> { typedef _Float16 t; };
-template <> struct OutOf<float> { typedef float t; };
-
-// VEC output elements as non-temporal stores of at most 16 B each
-template <typename OT, int VEC> __device__ __forceinline__ void store_out_nt(OT *p, const OT (&o)[VEC]) {
-  if constexpr (VEC * sizeof(OT) <= 16) {
-    vstore_nt<OT, VEC>(p, o);
-  } else {
-    constexpr int PER = 16 / sizeof(OT);
-#pragma unroll
-    for (int c = 0; c < VEC / PER; ++c) {
-      OT part[PER];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) part[k] = o[c * PER + k];
-      vstore_nt<OT, PER>(p + c * PER, part);
-    }
-  }
-}
-
 // ------------------------------------------------------------------ rows --
 struct RowsArgs {
   int64_t O, R;
   int64_t sp, dp;  // elements between row starts of src / dst (>= R)
   int64_t row0;    // first row of this launch (launches split at the grid limit)
-  int32_t scale;   // 0: x - mean, 1: (x - mean) / std
+  int32_t scale;   // 0: x - mean, 1: (x - mean) / std, 2: (x - mean) / (mean + offset)
+  double offset;   // scale 2 (bm_normalize_rows' mean baseline)
 };
 
 // the sum of x over the row's threads, in every thread: lanes in lane order
@@ -143,7 +127,9 @@ __global__ void __launch_bounds__(kThreads)
   }
   const double mean = P + row_sum<WPR>(s1, lane, wave, sm) / n;
   double sd = 1.0;
-  if (a.scale) {
+  if (a.scale == 2) {
+    sd = mean + a.offset;  // bm_normalize_rows: the baseline is the mean
+  } else if (a.scale) {
     double t1 = 0.0, t2 = 0.0;
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
@@ -161,7 +147,8 @@ __global__ void __launch_bounds__(kThreads)
     sd = sqrt((m2 < 0.0 ? 0.0 : m2) / n);  // (a nan stays a nan)
   }
   // the one write
-  const double inv = kRecip ? 1.0 / sd : 0.0;
+  const bool recip = kRecip && a.scale == 1;
+  const double inv = recip ? 1.0 / sd : 0.0;
 #pragma unroll
   for (int u = 0; u < NV; ++u) {
     if (j0 + u * stride < a.R) {
@@ -169,7 +156,7 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         const double d = to_f64(v[u][k]) - mean;
-        ov[k] = (OT)(a.scale ? (kRecip ? d * inv : d / sd) : d);
+        ov[k] = (OT)(a.scale ? (recip ? d * inv : d / sd) : d);
       }
       store_out_nt<OT, VEC>(o + j0 + u * stride, ov);
     }
@@ -310,6 +297,27 @@ int check_dtypes(const char *who, int in_dtype, int out_dtype) {
 
 }  // namespace
 
+// bm_standardize_rows behind its argument checks: the plan and the launch.
+// Also bm_normalize_rows' mean baseline (bm_quantile.hip), mode 2 with `offset`.
+int bm_standardize_rows_checked(const char *who, const void *src, int in_dtype, int64_t O, int64_t R,
+                                int64_t src_pitch, void *dst, int out_dtype, int64_t dst_pitch, int mode,
+                                double offset, int *taken, hipStream_t stream) {
+  *taken = 1;
+  if (O == 0 || R == 0) return BM_OK;  // nothing to write
+  const int ies = dtype_size(in_dtype), oes = dtype_size(out_dtype);
+  const int vec = std_vec(ies, oes, R, src_pitch, dst_pitch, src, dst);
+  const int64_t held = (int64_t)vec * lane_vecs(vec);  // elements a thread holds
+  const bool wave = R <= 64 * held;
+  if (!wave && (R > kThreads * held || O < kBlockMinRows)) {
+    *taken = 0;  // rows beyond the registers, or too few of them for a block each (see the plan above)
+    return BM_OK;
+  }
+  RowsArgs a{};
+  a.O = O; a.R = R; a.sp = src_pitch; a.dp = dst_pitch; a.scale = mode; a.offset = offset;
+  launch_rows(in_dtype, vec, !wave, src, dst, a, stream);
+  return check_launch(who);
+}
+
 extern "C" int bm_standardize_rows(const void *src, int in_dtype, int64_t O, int64_t R, int64_t src_pitch,
                                    void *dst, int out_dtype, int64_t dst_pitch, int scale, int *taken,
                                    void *stream) {
@@ -327,20 +335,8 @@ extern "C" int bm_standardize_rows(const void *src, int in_dtype, int64_t O, int
                  (long long)src_pitch, (long long)dst_pitch, (long long)R);
     return BM_E_ARG;
   }
-  *taken = 1;
-  if (O == 0 || R == 0) return BM_OK;  // nothing to write
-  const int ies = dtype_size(in_dtype), oes = dtype_size(out_dtype);
-  const int vec = std_vec(ies, oes, R, src_pitch, dst_pitch, src, dst);
-  const int64_t held = (int64_t)vec * lane_vecs(vec);  // elements a thread holds
-  const bool wave = R <= 64 * held;
-  if (!wave && (R > kThreads * held || O < kBlockMinRows)) {
-    *taken = 0;  // rows beyond the registers, or too few of them for a block each (see the plan above)
-    return BM_OK;
-  }
-  RowsArgs a{};
-  a.O = O; a.R = R; a.sp = src_pitch; a.dp = dst_pitch; a.scale = scale;
-  launch_rows(in_dtype, vec, !wave, src, dst, a, (hipStream_t)stream);
-  return check_launch(who);
+  return bm_standardize_rows_checked(who, src, in_dtype, O, R, src_pitch, dst, out_dtype, dst_pitch, scale, 0.0, taken,
+                                     (hipStream_t)stream);
 }
 
 extern "C" int bm_standardize_apply(const void *src, int in_dtype, int64_t O, int64_t R, int64_t I,

@@ -10,6 +10,28 @@
 template <typename T> __device__ __forceinline__ double to_f64(T x) { return (double)x; }
 template <> __device__ __forceinline__ double to_f64<_Float16>(_Float16 x) { return (double)(float)x; }
 
+// ---- the statistics dtype of an element type, and its stores ----
+// the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
+template <typename T> struct OutOf { typedef double t; };
+template <> struct OutOf<_Float16> { typedef _Float16 t; };
+template <> struct OutOf<float> { typedef float t; };
+
+// VEC output elements as non-temporal stores of at most 16 B each
+template <typename OT, int VEC> __device__ __forceinline__ void store_out_nt(OT *p, const OT (&o)[VEC]) {
+  if constexpr (VEC * sizeof(OT) <= 16) {
+    vstore_nt<OT, VEC>(p, o);
+  } else {
+    constexpr int PER = 16 / sizeof(OT);
+#pragma unroll
+    for (int c = 0; c < VEC / PER; ++c) {
+      OT part[PER];
+#pragma unroll
+      for (int k = 0; k < PER; ++k) part[k] = o[c * PER + k];
+      vstore_nt<OT, PER>(p + c * PER, part);
+    }
+  }
+}
+
 // ---- wave fold through DPP ----
 // A 64-bit lane value moved by a DPP modifier of v_mov (two 32-bit halves, the
 // same source lane): the cross-lane read stays in the VALU, no LDS round trip

@@ -19,6 +19,7 @@ CO_COV, CO_CORR = 0, 1   # BM_CO_COV, BM_CO_CORR
 COMOMENT_MAX_SIGNALS = 4   # BM_COMOMENT_MAX_SIGNALS
 COMOMENT_MAX_PARTS = 128   # BM_COMOMENT_MAX_PARTS
 QUANTILE_MAX_RANKS = 8     # BM_QUANTILE_MAX_RANKS
+NORM_MEAN, NORM_RANK = 0, 1  # BM_NORM_MEAN, BM_NORM_RANK
 
 LIB_PATH = os.environ.get("BOLT_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "libbolt_mi355x.so")  # env: A/B builds
@@ -90,6 +91,9 @@ SIGNATURES = {
                                                _c.POINTER(_c.c_size_t)]),
     "bm_quantile_select": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _i64p, _f64p,
                                       _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "bm_normalize_rows": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64,
+                                     _c.c_double, _c.c_double, _c.c_void_p, _c.c_int, _c.c_int64,
+                                     _c.POINTER(_c.c_int), _c.c_void_p]),
     "bm_comm_unique_id": (_c.c_int, [_c.c_void_p, _c.c_size_t]),
     "bm_comm_init": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_void_p, _c.c_int]),
     "bm_comm_destroy": (_c.c_int, [_c.c_void_p]),

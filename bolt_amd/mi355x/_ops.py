@@ -498,6 +498,21 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_quantile_select")
 
+    def normalize_rows(self, src, code, O, R, src_pitch, baseline, rank, frac, offset, dst, out_code, dst_pitch):
+        """dst rows = (src rows - b) / (b + offset) with b each row's own
+        baseline -- ``baseline`` _lib.NORM_MEAN: its mean; _lib.NORM_RANK: the
+        order statistic ``rank`` / ``frac`` as one quantile of quantile_rows --
+        O rows of R elements, pitches in elements: one read and one write
+        (bm_normalize_rows) -> True if the rows were taken, False (nothing
+        launched) when they do not fit the kernels."""
+        taken = ctypes.c_int(0)
+        rc = self.lib.bm_normalize_rows(src.data_ptr(), code, O, R, src_pitch, baseline, rank, frac, offset,
+                                        dst.data_ptr(), out_code, dst_pitch, ctypes.byref(taken),
+                                        raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_normalize_rows")
+        return bool(taken.value)
+
     def state_bytes(self, stat, code, nout):
         n = ctypes.c_size_t(0)
         _lib.check(self.lib.bm_reduce_state_bytes(stat, code, nout, ctypes.byref(n)), "bm_reduce_state_bytes")

@@ -1395,13 +1395,27 @@ class BoltArrayMI355X(BoltArray):
             tensors, _, planes = reduction.outputs(be, dev, f64, len(want), nplane, False)
             reduction.combine_moments(be, code, fcode, want, states, counts, nplane, tensors)
 
+        if not nloc:
+            return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+        return self._apply_planes(plan, src, planes[:nplane * 8],
+                                  planes[nplane * 8:2 * nplane * 8] if scale else None, out_dtype, ocode)
+
+    def _apply_planes(self, plan, src, mean, std, out_dtype, ocode):
+        """_standardized's and _normalized's second half: (x - mean) [/ std]
+        over ``src`` (reduction.source of ``plan``, compact) with the float64
+        device planes ``mean`` / ``std`` (None: centre only) of O*I values
+        (bm_standardize_apply: one read and one write), permuted back where
+        the source was permuted -> the result array."""
+        be, dev = self._backend, self._device
+        perm, O, R, I, nloc = plan.perm, plan.O, plan.R, plan.I, plan.nloc
+        es, oes = self._dtype.itemsize, out_dtype.itemsize
+        f64 = np.dtype(np.float64)
+        scale = std is not None
         dst = _empty(nloc * oes, dev)
         if nloc:
             src, pitch = src.buf, src.pitch
-            mean = planes[:nplane * 8]
-            std = planes[nplane * 8:2 * nplane * 8] if scale else None
             if hasattr(be, "standardize_apply"):
-                be.standardize_apply(src, code, O, R, I, pitch, mean, std, dst, ocode, R)
+                be.standardize_apply(src, plan.code, O, R, I, pitch, mean, std, dst, ocode, R)
             else:
                 # an executor without the entry points (the CPU test executor):
                 # torch float64 arithmetic on views of the bytes, padded rows
@@ -1439,6 +1453,153 @@ class BoltArrayMI355X(BoltArray):
         variance gives nan (0/0, as numpy), a record holding a nan gives nan
         throughout.  An addition to the reference's API."""
         return self._standardized(axis, True)
+
+    def _normalized(self, axis, method, perc, offset):
+        """normalize(): every record over ``axis`` against its own baseline b,
+        (x - b) / (b + offset), as a new device array of this array's shape and
+        split in the dtype of ``record - 0.0``.  b is float64: the mean as
+        _standardized forms it, or the 'linear' percentile as _quantile does,
+        unrounded.
+
+        Planned with reduction.plan_for like _standardized, and what it costs:
+          * the last axis (rows dense or row-padded, read in place), every
+            record on this rank: one bm_normalize_rows launch, one read and
+            one write; a padded input whose item size is kept gives a result
+            padded alike;
+          * rows that launch does not take, and every other layout: the
+            float64 baseline plane in HBM first, then bm_standardize_apply
+            with mean = b and std = b + offset (one float64 add on the plane):
+            one read and one write on top of the plane's cost.  The plane of
+            'mean' is _standardized's (one read; the sharded axis reduced:
+            per-rank states, gathered and merged in rank order).  The plane of
+            'percentile' is _quantile's rows -- read in place where the
+            reduced axes are the rows (one read for rows the registers hold,
+            else sizeof(element) reads), else after one permute into a dense
+            temporary with the kept axes first (one more read and write) --
+            and stays on the device; only across ranks with the sharded axis
+            reduced does it come through the host, as quantile()'s result
+            (one exchange, one gather, one upload);
+          * reduced axes that are not one block: the source permuted to the
+            front for the apply and the result permuted back -- two more reads
+            and writes; a row-padded input over other axes than the last:
+            copied to a dense temporary first -- one more read and write.
+        Moment states (KEEP_MOMENTS, swap states) are neither used nor left."""
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        if method not in ('percentile', 'mean'):
+            raise ValueError("normalize: method must be 'percentile' or 'mean', got %r (thunder's sliding-window "
+                             "baselines 'window' and 'window-exact' are not offered)" % (method,))
+
+        def real(v, name, lo=None, hi=None):
+            try:
+                a = np.asarray(v)
+            except Exception:
+                a = None
+            if a is None or a.dtype.kind not in "biuf" or a.ndim != 0 or not np.isfinite(a) \
+                    or (lo is not None and not lo <= a <= hi):
+                raise ValueError("normalize: %s must be a finite real scalar%s, got %r"
+                                 % (name, "" if lo is None else " in [%g, %g]" % (lo, hi), v))
+            return float(a)
+        offset = real(offset, "offset")
+        rank_baseline = method == 'percentile'
+        if rank_baseline:
+            perc = real(perc, "perc", 0, 100)
+        plan, out_dtype, ocode = reduction.plan_for(self, ax, reduction.STANDARDIZE)
+        if rank_baseline and plan.world > 1 and 0 in plan.axes and len(plan.axes) == self.ndim:
+            raise NotImplementedError("normalize(method='percentile') over every axis of an array sharded across %d "
+                                      "ranks needs a distributed select; reduce the sharded axis together with "
+                                      "fewer axes, or use method='mean'" % plan.world)
+        code = plan.code
+        dev = self._device
+        if self.size == 0:
+            return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+        rank, frac = 0, 0.0
+        if rank_baseline:
+            # pos = (perc / 100) (n - 1) in float64, as _quantile: lo the floor(pos)-th smallest, g the rest
+            pos = np.float64(perc) / 100 * (self._nrecords(ax) - 1)
+            rank, frac = int(np.floor(pos)), float(pos - np.floor(pos))
+        be = backend_for(dev)
+        perm, O, R, I, nloc = plan.perm, plan.O, plan.R, plan.I, plan.nloc
+        es, oes = self._dtype.itemsize, out_dtype.itemsize
+        d = self.__dict__
+        pbuf, P = d.get("_pbuf"), d.get("_pitch")
+        # every reduced record lies whole on this rank
+        local = plan.world == 1 or 0 not in plan.axes
+        # the reduced axis is the last one: rows, a pitch apart
+        rows_last = perm is None and I == 1 and local and (pbuf is None or R == plan.lshape[-1])
+
+        if rows_last and nloc and hasattr(be, "normalize_rows"):
+            keep_pad = pbuf is not None and oes == es
+            dp = P if keep_pad else R
+            dst = _empty(O * dp * oes, dev)
+            src, sp = (pbuf, P) if pbuf is not None else (self._data, R)
+            if be.normalize_rows(src, code, O, R, sp, _lib.NORM_RANK if rank_baseline else _lib.NORM_MEAN, rank, frac,
+                                 offset, dst, ocode, dp):
+                if not keep_pad:
+                    return self._like(dst, self._shape, self._split, dtype=out_dtype)
+                new = self._derive_padded(dst, P, self._shape, self._split)
+                new.__dict__["_dtype"] = out_dtype
+                return new
+
+        # the float64 baseline plane in HBM (a rank with an empty slab launches
+        # nothing but takes part in every collective)
+        f64 = np.dtype(np.float64)
+        fcode = dtype_code(f64)
+        base = None
+        src = reduction.source(self, plan, compact=True) if nloc else None
+        if not rank_baseline:
+            if local:
+                if nloc:
+                    tensors, _, base = reduction.outputs(be, dev, f64, 1, O * I, False)
+                    reduction.launch_moments(be, src, es, code, fcode, ('mean',), tensors)
+            else:
+                states, counts = reduction.sharded_states(self._ctx, be, dev, plan, _lib.STAT_VAR, src)
+                tensors, _, base = reduction.outputs(be, dev, f64, 1, plan.nout, False)
+                reduction.combine_moments(be, code, fcode, ('mean',), states, counts, plan.nout, tensors)
+        elif local:
+            if nloc:
+                qbuf, qpitch, qO, qR = self._quantile_rows(plan)
+                base = reduction.quantile_baseline(be, qbuf, self._dtype, code, qO, qR, qpitch, rank, frac)
+        else:
+            # the sharded axis is reduced with other axes kept: quantile()'s
+            # exchange and gather; every rank ends with the whole plane
+            ranks, fr, qdt = reduction.baseline_request(self._dtype, rank, frac)
+            host = reduction.baseline_f64(self._quantile_planes(plan, qdt, dtype_code(qdt), ranks, fr), frac)
+            if nloc:
+                import torch
+                from bolt_amd.mi355x import functional as F
+                base = F.as_bytes(torch.from_numpy(np.ascontiguousarray(host)).to(dev))
+        if not nloc:
+            return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+        from bolt_amd.mi355x import functional as F
+        den = F.as_bytes(F.view(base, (-1,), f64) + offset)
+        return self._apply_planes(plan, src, base, den, out_dtype, ocode)
+
+    def normalize(self, axis=None, method='percentile', perc=20, offset=0.1):
+        """Every record over ``axis`` (None: every axis; taken as mean() takes
+        it) against its own baseline b: ``(x - b) / (b + offset)``, the dF/F of
+        a calcium-imaging pipeline (thunder's Series.normalize), as a new array
+        of the same shape, split and sharding, resident on the device; its
+        dtype is that of ``record - 0.0`` (float16 / float32 keep theirs, every
+        other dtype gives float64), as zscore() returns its result.  The
+        baseline is float64 and is not rounded to that dtype: ``method``
+        'percentile' takes the ``perc``-th percentile with 'linear'
+        interpolation -- quantile()'s lo + (hi - lo) g with
+        pos = (perc / 100)(n - 1), g == 0 giving lo -- and 'mean' the mean as
+        center() forms it.  x - b, b + offset and the division (a true one)
+        are three separately rounded float64 operations, nothing is fused, and
+        the result is rounded once.  A record holding a NaN is NaN throughout;
+        b + offset == 0 gives what IEEE gives (inf, or nan for 0/0), as numpy;
+        int64 / uint64 values beyond 2^53 round when converted to float64; bool
+        runs as uint8.  ``method`` other than the two, ``perc`` not a finite
+        real scalar in [0, 100] and ``offset`` not a finite real scalar raise
+        ValueError before any device work; 'percentile' over every axis of an
+        array sharded over more than one rank raises NotImplementedError, as
+        quantile() does.  thunder's sliding-window baselines ('window',
+        'window-exact') are out of scope.  Over the last axis the array is
+        read once and written once; what other layouts cost: _normalized.  An
+        addition to the reference's API."""
+        return self._normalized(axis, method, perc, offset)
 
     def _comoment(self, y, axis, keepdims, what):
         """cov / corr (``what``: _lib.CO_COV / CO_CORR) of every record over
@@ -1678,6 +1839,38 @@ class BoltArrayMI355X(BoltArray):
             tmp = self._like(data, tuple(self._shape[p] for p in gperm), len(kept))
             tplan, _, _ = reduction.plan_for(tmp, tuple(range(len(kept), self.ndim)), reduction.QUANTILE)
             return tmp._quantile_planes(tplan, out_dtype, ocode, ranks, frac)
+        buf, pitch, O, R = self._quantile_rows(plan)
+        nloc = plan.nloc
+        dev = self._device
+        be = backend_for(dev)
+        single = plan.world == 1
+        run = O and nloc
+        planes = []
+        k0 = 0
+        while k0 < len(ranks):
+            k1, S = k0, 0
+            while k1 < len(ranks) and S + (2 if frac[k1] != 0.0 else 1) <= _lib.QUANTILE_MAX_RANKS:
+                S += 2 if frac[k1] != 0.0 else 1
+                k1 += 1
+            Kb = k1 - k0
+            outs = reduction.outputs(be, dev, out_dtype, Kb, O, single and run and
+                                     Kb * O * out_dtype.itemsize <= reduction.HOST_RESULT_MAX)
+            if run:
+                reduction.quantile_rows(be, buf, self._dtype, plan.code, O, R, pitch, ranks[k0:k1], frac[k0:k1],
+                                        outs[2] if outs[2] is not None else outs[1], out_dtype, ocode)
+            planes += reduction.finish(outs, dev, plan, out_dtype, Kb, O, None, None if single else ctx)
+            k0 = k1
+        return planes
+
+    def _quantile_rows(self, plan):
+        """This rank's records over ``plan``'s reduced axes as rows (every
+        record whole on this rank) -> (buffer, row pitch in elements, O rows,
+        R elements a row): the array itself where the reduced axes are its
+        rows, dense or a pitch apart, else a dense temporary with the kept axes
+        first, in ascending order, and the reduced axes last (one bm_permute,
+        or one strided copy out of padded rows)."""
+        es = self._dtype.itemsize
+        d = self.__dict__
         lshape, nloc = plan.lshape, plan.nloc
         R = int(np.prod([lshape[a] for a in plan.axes], dtype=np.int64))
         O = nloc // R if R else 0
@@ -1698,24 +1891,7 @@ class BoltArrayMI355X(BoltArray):
                                 es)
             elif nloc:
                 be.permute(d["_data"], lshape, perm, es, buf)
-        single = plan.world == 1
-        run = O and nloc
-        planes = []
-        k0 = 0
-        while k0 < len(ranks):
-            k1, S = k0, 0
-            while k1 < len(ranks) and S + (2 if frac[k1] != 0.0 else 1) <= _lib.QUANTILE_MAX_RANKS:
-                S += 2 if frac[k1] != 0.0 else 1
-                k1 += 1
-            Kb = k1 - k0
-            outs = reduction.outputs(be, dev, out_dtype, Kb, O, single and run and
-                                     Kb * O * out_dtype.itemsize <= reduction.HOST_RESULT_MAX)
-            if run:
-                reduction.quantile_rows(be, buf, self._dtype, plan.code, O, R, pitch, ranks[k0:k1], frac[k0:k1],
-                                        outs[2] if outs[2] is not None else outs[1], out_dtype, ocode)
-            planes += reduction.finish(outs, dev, plan, out_dtype, Kb, O, None, None if single else ctx)
-            k0 = k1
-        return planes
+        return buf, pitch, O, R
 
     def quantile(self, q, axis=None, keepdims=False, method='linear'):
         """The ``q``-quantile(s) of every record over ``axis`` (None: every

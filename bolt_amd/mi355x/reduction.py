@@ -1,7 +1,8 @@
 """Mechanics of the statistics: how the reduced axes of an array lie in HBM and
 what is launched to reduce over them.  One plan, one source, one finish, for
 array.py's _reduced (one statistic), _reduced_moments (stats()),
-_standardized (center / zscore), _comoment (cov / corr) and _quantile (quantile / percentile / median).  The rules -- what is kept, padded or fused,
+_standardized (center / zscore), _normalized (normalize), _comoment (cov / corr)
+and _quantile (quantile / percentile / median).  The rules -- what is kept, padded or fused,
 and their switches -- stay in array.py; this module never imports it and is
 handed the array.
 """
@@ -423,6 +424,47 @@ def quantile_rows(be, buf, dtype, code, O, R, pitch, ranks, frac, out, out_dtype
         if dtype.kind == "f":
             val = np.where(torch.isnan(srt[:, R - 1]).cpu().numpy(), np.nan, val)
         res[k] = torch.from_numpy(np.ascontiguousarray(val.astype(out_dtype))).to(res.device)
+
+
+def baseline_request(dtype, rank, frac):
+    """What to ask quantile_rows for so that the 'linear' quantile (``rank``,
+    ``frac``) can be had in float64, unrounded -> (ranks, frac, out dtype).
+    Where the statistics dtype is float64 that is the quantile itself.
+    float16 / float32 keep theirs, and bm_quantile_rows gives no other, so a
+    rounded interpolation is all it has: lo and hi are asked for as elements,
+    bit for bit, and baseline_f64 interpolates."""
+    dt = np.dtype(dtype)
+    if stat_dtype(dt, (1,)) == np.float64:
+        return [rank], [frac], np.dtype(np.float64)
+    return ([rank, rank + 1], [0.0, 0.0], dt) if frac != 0.0 else ([rank], [0.0], dt)
+
+
+def baseline_f64(planes, frac):
+    """baseline_request's planes (numpy arrays or tensors, lo [, hi]) -> the
+    float64 baseline: lo, or lo + (hi - lo) * frac as three separately rounded
+    float64 operations (bm_quantile.hip's emit; a NaN row's lo is NaN)."""
+    wide = (lambda p: p.astype(np.float64)) if isinstance(planes[0], np.ndarray) else (lambda p: p.double())
+    lo = wide(planes[0])
+    if len(planes) == 1:
+        return lo
+    with np.errstate(all="ignore"):
+        d = wide(planes[1]) - lo
+        t = d * frac
+        return lo + t
+
+
+def quantile_baseline(be, buf, dtype, code, O, R, pitch, rank, frac):
+    """The float64 'linear' quantile (``rank``, ``frac``) of O rows of ``buf``
+    as a device plane of O values (uint8 tensor): quantile_rows into HBM, no
+    host round trip."""
+    from bolt_amd.mi355x import functional as F
+    ranks, fr, odt = baseline_request(dtype, rank, frac)
+    out = _empty(len(ranks) * O * odt.itemsize, buf.device)
+    quantile_rows(be, buf, dtype, code, O, R, pitch, ranks, fr, out, odt, dtype_code(odt))
+    if odt == np.float64:
+        return out
+    planes = F.view(out, (len(ranks), O), odt)
+    return F.as_bytes(baseline_f64([planes[k] for k in range(len(ranks))], frac))
 
 
 def merge_equal_counts(planes, Rl, nrows):

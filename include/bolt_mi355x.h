@@ -571,6 +571,42 @@ int bm_quantile_select(const void *src, int in_dtype, int64_t O, int64_t R,
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * bm_normalize_rows -- every row against its own baseline b_o in one read and
+ * one write (dF/F of a calcium-imaging pipeline):
+ *   dst[o*dst_pitch + r] = (src[o*src_pitch + r] - b_o) / (b_o + offset),  r < R.
+ * No reference call site: an API addition (thunder's Series.normalize does the
+ * step on the host).  Pitches are in elements, >= R; the pad is neither read
+ * nor written.  out_dtype must be the statistics dtype of in_dtype (float16 /
+ * float32 keep theirs, every other dtype gives float64).  The baseline is
+ *   BM_NORM_MEAN: the float64 mean of the row, formed as bm_standardize_rows
+ *     forms it; rank and frac are ignored; *taken follows bm_standardize_rows'
+ *     plan;
+ *   BM_NORM_RANK: the order statistic given by rank and frac as one quantile
+ *     of bm_quantile_rows -- frac in [0, 1), rank (+ 1 where frac != 0) below
+ *     R -- that is lo, or lo + (hi - lo) * frac in float64, not rounded to
+ *     out_dtype.  The row is held in registers as bm_quantile_rows' keys, the
+ *     rank found by its bit search, and the held keys are decoded back to the
+ *     values; *taken follows bm_quantile_rows' plan, where the vector width
+ *     must also divide dst_pitch.
+ * x - b, b + offset and the (true) division are three separately rounded
+ * float64 operations, rounded once to out_dtype.  A row holding a NaN is NaN
+ * throughout; b + offset == 0 gives what IEEE gives.  bool runs as uint8.
+ * *taken = 1 when the rows were written; *taken = 0 and nothing launched when
+ * the plan does not hold them (a baseline plane, then bm_standardize_apply
+ * with mean = b and std = b + offset, serve those).  O == 0 or R == 0 writes
+ * nothing (*taken = 1).  Arguments are checked before any launch: null
+ * pointers, a bad dtype or out_dtype, negative extents, a pitch below R, a
+ * baseline that is neither of the two, a bad rank or frac and a non-finite
+ * offset give BM_E_ARG and leave *taken alone.
+ */
+#define BM_NORM_MEAN 0
+#define BM_NORM_RANK 1
+int bm_normalize_rows(const void *src, int in_dtype, int64_t O, int64_t R,
+                      int64_t src_pitch, int baseline, int64_t rank,
+                      double frac, double offset, void *dst, int out_dtype,
+                      int64_t dst_pitch, int *taken, void *stream);
+
+/*
  * ---------------------------------------------------------------------------
  * Multi-GPU record exchange over RCCL (xGMI), one process per GPU.
  *
