@@ -365,6 +365,81 @@ __global__ void __launch_bounds__(kThreads)
         const int lane = threadIdx.x & 63;
         T *const p0 = q + ib + (dof + (a0 + uy) * d.da) * mo.pitch;
         const int64_t pstep = (int64_t)RPB * d.da * mo.pitch;
+        if constexpr (UNMASKED) {
+          // The two LDS-bound kernels run one wave per SIMD and block, so what
+          // that wave waits for nobody fills.  Their pairs' results stay in
+          // registers (NS / 2 x (s1, s2, pivot word): these kernels have ~100
+          // VGPRs to spare at two blocks per CU) and reach mst once, after the
+          // last pair.  The predicated LDS writes after every pair cut the
+          // store phase into one basic block per pair: each pair then began
+          // with its LDS reads and ended with its own folds.  As one block the
+          // compiler issues a pair's stores ahead of the sums before them and
+          // folds all the pairs together at the end, sixteen DPP chains side
+          // by side.  The same adds in the same order as below.
+          constexpr bool FULL = decltype(full)::value;
+          constexpr int NP = NS / 2;
+          double r1[NP], r2[NP];
+          F rk[NP];  // the pivot stays an F word until it is written
+#pragma unroll
+          for (int ip = 0; ip < NP; ++ip) {
+            // both rows' tile words and pivot words first, then their use
+            T w[2][VB], kw[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int ra = uy + (2 * ip + h) * RPB;
+#pragma unroll
+              for (int k = 0; k < VB; ++k) w[h][k] = tile[ib + k][ra];
+              kw[h] = tile[0][ra];
+            }
+            double s1[2], s2[2];
+            F kf[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int it = 2 * ip + h;
+              if (FULL || uy < na - it * RPB) {
+                T *p = p0 + it * pstep;
+                if (FULL || ib <= nb - VB) {
+                  vstore_nt<T, VB>(p, w[h]);
+                } else {
+#pragma unroll
+                  for (int k = 0; k < VB; ++k)
+                    if (ib < nb - k) p[k] = w[h][k];
+                }
+              }
+              const F k0 = __builtin_bit_cast(F, kw[h]);
+              kf[h] = __builtin_isfinite(k0) ? k0 : F(0);
+              const double K = (double)kf[h];
+              s1[h] = 0.0;
+              s2[h] = 0.0;
+#pragma unroll
+              for (int k = 0; k < VB; ++k) {
+                const double y = (FULL || ib < nb - k) ? (double)__builtin_bit_cast(F, w[h][k]) - K : 0.0;
+                s1[h] += y;
+                s2[h] = fma(y, y, s2[h]);
+              }
+            }
+            rk[ip] = (lane & 8) ? kf[1] : kf[0];
+            r1[ip] = pair_fold16(s1[0], s1[1], lane);
+            r2[ip] = pair_fold16(s2[0], s2[1], lane);
+          }
+          if ((lane & 7) == 0) {  // lane 0 of a segment: the pairs' even rows, lane 8: the odd ones
+            const int seg = ux / 16;
+#pragma unroll
+            for (int ip = 0; ip < NP; ++ip) {
+              const int ra = uy + 2 * ip * RPB, rr = (lane & 8) ? ra + RPB : ra;
+              mst[rr * NSEG + seg] = r1[ip];
+              mst[(TA + rr) * NSEG + seg] = r2[ip];
+            }
+            if (seg == 0) {
+#pragma unroll
+              for (int ip = 0; ip < NP; ++ip) {
+                const int ra = uy + 2 * ip * RPB, rr = (lane & 8) ? ra + RPB : ra;
+                mst[2 * TA * NSEG + rr] = (double)rk[ip];
+              }
+            }
+          }
+          return;
+        }
 #pragma unroll
         for (int it = 0; it < NS; it += 2) {
           const int ra = uy + it * RPB;
