@@ -23,6 +23,12 @@
 //     row phases, chunks and ranks, always in a fixed order (deterministic).
 //   mean: pivot-shifted sums around the (row, chunk)'s first element,
 //     mean = K + S1/n (no cancellation: the error is eps-relative to max|x|).
+//   Pivots are finite: a first element that is an infinity or a NaN takes 0
+//     (finite_or_zero), so a row with such a value has the mean a sum over it
+//     gives (numpy's: inf, -inf, or NaN for inf - inf or a NaN) wherever the
+//     value sits, and NaN var / std (m2_out).  Welford and Chan means that come
+//     out NaN are recomputed as sums, on that path only.  (Overflow of x - K
+//     for finite values near +-1.8e308 is not handled.)
 //   SUM over floats is a float64 sum; over integers a uint64 modular sum
 //   truncated to the input width; over bool an OR.
 // All are HBM-bound: algorithmic bytes = N*elem_bytes + nout*out_bytes.
@@ -358,6 +364,19 @@ __device__ __forceinline__ double m2_out(double m2, double mean) {
   return mean - mean == 0.0 ? (m2 > 0.0 ? m2 : 0.0) : __builtin_nan("");
 }
 
+// The NaN path of a Welford mean.  An infinity among the values leaves the
+// state's mean NaN unless it is in the last batch merged (the batch's own
+// pivot, then every merge's delta, is inf - inf), where a sum over the values
+// gives the infinity.  So a mean that came out NaN is formed again as
+// sum(x - P) / n over the n values `stride` apart (P is finite): +-inf, or
+// NaN for inf - inf or a NaN among them.  Finite data never comes here.
+template <typename T>
+__device__ __forceinline__ double summed_mean_y(const T *p, int64_t stride, int64_t n, double P) {
+  double s = 0.0;
+  for (int64_t r = 0; r < n; ++r) s += to_f64(p[r * stride]) - P;
+  return s / (double)n;
+}
+
 // the kept copy of the var / std state of output idx: bm_reduce_state's values
 __device__ __forceinline__ void emit_kept(const Sink &sk, int64_t idx, double mean_y, double m2, double P) {
   sk.k0[idx] = P + mean_y;
@@ -464,7 +483,7 @@ __global__ void __launch_bounds__(kThreads)
       T p0v[VEC];
       vload<T, VEC>(base, p0v);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) P[k] = to_f64(p0v[k]);
+      for (int k = 0; k < VEC; ++k) P[k] = finite_or_zero(to_f64(p0v[k]));
     }
     if (MODE == M_MEANMOM) {
       // never chunked (r_lo == 0): the mean's pivot, the chunk's first row, is P
@@ -477,7 +496,7 @@ __global__ void __launch_bounds__(kThreads)
       T k0[VEC];
       vload<T, VEC>(base + r_lo * d.I, k0);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[k].pivot(to_f64(k0[k]));
+      for (int k = 0; k < VEC; ++k) acc[k].pivot(finite_or_zero(to_f64(k0[k])));
     }
     if constexpr (mean_part<MODE>() || MODE == M_MOM || facc_mode<MODE>()) {
       // kColsUnroll rows in flight per lane; the adds stay in row order
@@ -598,6 +617,8 @@ __global__ void __launch_bounds__(kThreads)
       for (int k = 0; k < VEC; ++k) {
         const int64_t e = (int64_t)o * d.I + col0 + k;
         const int64_t idx = sk.final_out ? e : (c * plane + e);
+        if (wm[k] != wm[k])  // a non-finite value in the column: the mean a sum gives
+          wm[k] = summed_mean_y(src + ((int64_t)o * d.R + r_lo) * d.I + col0 + k, d.I, r_hi - r_lo, P[k]);
         emit_mom(sk, idx, e, c, ntot, wm[k], wq[k], P[k]);
       }
       return;
@@ -644,7 +665,8 @@ __global__ void __launch_bounds__(kThreads)
     const int64_t e = (int64_t)o * d.I + col0 + k;
     const int64_t idx = sk.final_out ? e : (c * plane + e);
     emit<MODE>(sk, idx, ntot, m_[k], 0.0, __builtin_bit_cast(uint64_t, m_[k]));
-    if constexpr (MODE == M_MEANMOM) emit_kept(sk, idx, wm[k], wq[k], P[k]);
+    // (a NaN Welford mean -- a non-finite value in the column -- gives way to the sums')
+    if constexpr (MODE == M_MEANMOM) emit_kept(sk, idx, wm[k] == wm[k] ? wm[k] : m_[k] - P[k], wq[k], P[k]);
   }
 }
 
@@ -685,8 +707,9 @@ __global__ void __launch_bounds__(kThreads)
   // var / std: every value is shifted by the row's first element P (shared
   // by all chunks of the row), so the Welford means stay near zero and keep
   // their digits on offset data (1e6 + N(0,1)); batches bound outliers.
-  if (mean_part<MODE>()) acc.pivot(to_f64(row[r_lo]));
-  const double P = mom_part<MODE>() ? to_f64(row[0]) : 0.0;
+  // (both pivots finite, see finite_or_zero)
+  if (mean_part<MODE>()) acc.pivot(finite_or_zero(to_f64(row[r_lo])));
+  const double P = mom_part<MODE>() ? finite_or_zero(to_f64(row[0])) : 0.0;
   // kRowsUnroll 16-B vectors in flight per lane (HBM latency cover), over
   // whole wave-wide steps only: every lane runs the same iterations, so a
   // step ends on a line boundary of a line-aligned row and no 128-B line is
@@ -795,21 +818,35 @@ __global__ void __launch_bounds__(kThreads)
   } else if constexpr (!mom_part<MODE>()) {
     us = wave_fold(us, lane, [](uint64_t a, uint64_t b) { return bop<T, MODE>(a, b); });
   }
-  if (lane != kFoldLane) return;
   const double ntot = (double)(r_hi - r_lo);
+  double my = 0.0;  // var / std: the chunk's mean - P from (S1, S2) around C
+  if constexpr (MODE == M_MOM) {
+    // in every lane, so that the NaN path below is taken by the whole wave: a
+    // non-finite value in the chunk, whose mean the wave then sums again
+    // (summed_mean_y's, the lanes striding the chunk)
+    my = C + lane_of<kFoldLane>(ws) / ntot;
+    if (my != my) {
+      double s = 0.0;
+      for (int64_t k = r_lo + lane; k < r_hi; k += 64) s += to_f64(row[k]) - P;
+      my = wave_fold(s, lane, [](double a, double b) { return a + b; }) / ntot;
+    }
+  }
+  if (lane != kFoldLane) return;
   const int64_t e = (int64_t)o;
   const int64_t idx = sk.final_out ? e : (c * d.O + e);
   if constexpr (MODE == M_MOM) {
     // (S1, S2) around C -> mean - P and M2
     const double q = fma(-ws, ws / ntot, wq);
-    emit_mom(sk, idx, e, c, ntot, C + ws / ntot, q, P);
+    emit_mom(sk, idx, e, c, ntot, my, q, P);
     return;
   }
   if (mean_part<MODE>()) m = mean_from_sums(ntot, acc.K, m);
   emit<MODE>(sk, idx, ntot, m, 0.0, us);
   if constexpr (MODE == M_MEANMOM) {
     const double q = fma(-ws, ws / ntot, wq);
-    emit_kept(sk, idx, C + ws / ntot, q, P);
+    my = C + ws / ntot;
+    // (a NaN Welford mean -- a non-finite value in the row -- gives way to the sums')
+    emit_kept(sk, idx, my == my ? my : m - P, q, P);
   }
 }
 
@@ -1010,6 +1047,20 @@ struct CombDesc {
   int64_t counts[kMaxParts];
 };
 
+// The NaN path of a merged mean, as k_red_merge_tiles has it: a part whose mean
+// is an infinity, followed by a finite part, makes chan's delta * f + mean
+// inf - inf.  The merged mean is then the sum of the parts' means (all around
+// one finite pivot, or absolute): +-inf, or NaN for inf - inf or a NaN part --
+// what a sum over the values gives.
+__device__ __forceinline__ double summed_part_means(const double *__restrict__ p0, const CombDesc &d, int64_t e) {
+  double s = 0.0;
+  for (int64_t p = 0; p < d.nparts; ++p) {
+    const int64_t nb = d.explicit_counts ? d.counts[p] : min(d.R, (p + 1) * d.rchunk) - p * d.rchunk;
+    if (nb > 0) s += p0[p * d.part_stride + e];
+  }
+  return s;
+}
+
 template <int MODE, typename T>
 __global__ void __launch_bounds__(kThreads)
     k_red_combine(const double *__restrict__ p0, const double *__restrict__ p1, CombDesc d, Sink sk) {
@@ -1053,6 +1104,9 @@ __global__ void __launch_bounds__(kThreads)
         u = first ? b : bop<T, MODE>(u, b);
       }
       first = false;
+    }
+    if constexpr (MODE == M_MEAN || MODE == M_MOM) {
+      if (m != m) m = summed_part_means(p0, d, e);
     }
     if constexpr (MODE == M_MOM) {
       const double P = d.pivots ? p1[d.nparts * d.part_stride + e] : 0.0;
@@ -1137,7 +1191,10 @@ __global__ void __launch_bounds__(kThreads)
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  const PartState r = sm[0];
+  PartState r = sm[0];
+  if constexpr (MODE == M_MEAN || MODE == M_MOM) {
+    if (!int_sums && r.m != r.m) r.m = summed_part_means(p0, d, e);
+  }
   if constexpr (MODE == M_MOM) {
     if (int_sums) {
       double mean, m2;

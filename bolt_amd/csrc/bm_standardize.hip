@@ -15,7 +15,8 @@
 //     ran before it (bm_reduce_moments): two reads and one write in all.
 // Numerics (all float64): the row is in hand, so the moments are the
 //   two-pass sums -- mean = P + sum(x - P) / n around the row's first element
-//   P, then with d = x - mean, M2 = sum d^2 - (sum d)^2 / n (the second term
+//   P (0 if that is not finite, so a row with an infinity has numpy's mean
+//   whatever the column it is in), then with d = x - mean, M2 = sum d^2 - (sum d)^2 / n (the second term
 //   removes the rounding of the mean) and std = sqrt(M2 / n), the population
 //   value of statcounter.py:109-130.  Lanes add their values in register order
 //   and fold through DPP in lane order (wave_fold), waves through LDS in wave
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(kThreads)
     if (j0 + u * stride < a.R) vload_nt<T, VEC>(s + j0 + u * stride, v[u]);
   }
   const double n = (double)a.R;
-  const double P = to_f64(s[0]);
+  const double P = finite_or_zero(to_f64(s[0]));  // (an infinite first value: the mean is the sum's, inf or nan)
   double s1 = 0.0;
 #pragma unroll
   for (int u = 0; u < NV; ++u) {

@@ -10,6 +10,12 @@
 template <typename T> __device__ __forceinline__ double to_f64(T x) { return (double)x; }
 template <> __device__ __forceinline__ double to_f64<_Float16>(_Float16 x) { return (double)(float)x; }
 
+// A pivot that sums are shifted by must be finite: x - K around an infinite or
+// NaN K is NaN (or the other infinity) for every x of the row, where a sum over
+// the row gives the infinity itself.  Such a first value takes 0 instead; a
+// finite one is kept as it is, so finite rows keep their bits.
+__device__ __forceinline__ double finite_or_zero(double k) { return k - k == 0.0 ? k : 0.0; }
+
 // ---- the statistics dtype of an element type, and its stores ----
 // the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
 template <typename T> struct OutOf { typedef double t; };

@@ -170,7 +170,8 @@ class CpuBackend(object):
     def reduce_rows(self, stat, src, code, O, R, pitch, out, out_code):
         assert pitch >= R
         x = _np(src).view(_CODES[code])[:O * pitch].reshape(O, pitch)[:, :R].reshape(O, R, 1)
-        self._finish(stat, code, self._planes(stat, code, x), float(R), out, out_code)
+        with np.errstate(all="ignore"):  # (rows that hold an infinity: inf - inf)
+            self._finish(stat, code, self._planes(stat, code, x), float(R), out, out_code)
 
     def state_bytes(self, stat, code, nout):
         mom = stat in (STAT_VAR, STAT_STD)  # max / min / sum / mean: one 8-byte plane
@@ -228,8 +229,10 @@ class CpuBackend(object):
             mb = part[:nout * 8].view(np.float64)
             qb = part[nout * 8:2 * nout * 8].view(np.float64) if mom else np.zeros(nout)
             if n == 0:
-                n, m, q = float(c), mb.copy(), qb.copy()
-            else:
+                n, m, q, msum = float(c), mb.copy(), qb.copy(), mb.copy()
+                continue
+            with np.errstate(invalid="ignore"):  # inf - inf of a part with an infinity
+                msum = msum + mb
                 tot = n + c
                 d = mb - m
                 m = m + d * (c / tot)
@@ -242,6 +245,11 @@ class CpuBackend(object):
         elif stat == STAT_SUM:
             planes = [acc_u] if dt.kind in 'iub' else [acc_f]
         else:
+            if n:
+                # the kernels' rule (summed_part_means): a part whose mean is an
+                # infinity, followed by a finite part, leaves the merged mean
+                # inf - inf; it is then the sum of the parts' means
+                m = np.where(np.isnan(m), msum, m)
             planes = [m, q]
         self._finish(stat, code, planes, n, out, out_code)
 
