@@ -24,6 +24,8 @@ static inline int dtype_size(int dt) {
   }
 }
 static inline bool is_float(int dt) { return dt == BM_F16 || dt == BM_F32 || dt == BM_F64; }
+// the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
+static inline int stat_dtype(int dt) { return dt == BM_F16 || dt == BM_F32 ? dt : BM_F64; }
 
 // blocks of `threads` threads one launch takes at most (HIP: grid * block threads < 2^32)
 constexpr int64_t max_blocks(int threads) { return 0xffffffffLL / threads; }

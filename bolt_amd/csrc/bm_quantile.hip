@@ -100,7 +100,6 @@ int kind_of(int dt) {
 uint64_t nan_above(int dt) {
   return dt == BM_F16 ? 0x7C00ull : dt == BM_F32 ? 0x7F800000ull : dt == BM_F64 ? 0x7FF0000000000000ull : ~0ull;
 }
-int stat_dtype(int dt) { return dt == BM_F16 || dt == BM_F32 ? dt : BM_F64; }
 
 // element bits -> key: xor with neg where the sign bit is set, else with pos
 // (floats: every bit / the sign bit; signed: the sign bit both; unsigned: 0).

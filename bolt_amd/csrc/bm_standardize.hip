@@ -62,9 +62,6 @@ constexpr bool kRecip = false;
 #endif
 constexpr int kMaxVec = 8;  // elements per vector at most (1-byte inputs: 8-B loads, 64 B of float64 out)
 
-// the dtype of record - 0.0 (plan.stat_dtype): float16 / float32 stay, the rest float64
-int stat_dtype(int dt) { return dt == BM_F16 || dt == BM_F32 ? dt : BM_F64; }
-
 // ------------------------------------------------------------------ rows --
 struct RowsArgs {
   int64_t O, R;
@@ -73,23 +70,6 @@ struct RowsArgs {
   int32_t scale;   // 0: x - mean, 1: (x - mean) / std, 2: (x - mean) / (mean + offset)
   double offset;   // scale 2 (bm_normalize_rows' mean baseline)
 };
-
-// the sum of x over the row's threads, in every thread: lanes in lane order
-// (wave_fold), then the row's waves in wave order through LDS
-template <int WPR> __device__ __forceinline__ double row_sum(double x, int lane, int wave, double *sm) {
-  x = wave_fold(x, lane, [](double a, double b) { return a + b; });
-  if constexpr (WPR == 1) {
-    return lane_of<kFoldLane>(x);
-  } else {
-    if (lane == kFoldLane) sm[wave] = x;
-    __syncthreads();
-    double t = sm[0];
-#pragma unroll
-    for (int w = 1; w < WPR; ++w) t += sm[w];
-    __syncthreads();  // sm is written again by the next sum
-    return t;
-  }
-}
 
 // WPR waves per row (1, or the block's 4), each thread holding NV vectors of
 // VEC elements: R <= 64 * WPR * VEC * NV (the host's plan), R % VEC == 0.

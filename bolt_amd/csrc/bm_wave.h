@@ -94,6 +94,25 @@ template <int L> __device__ __forceinline__ double lane_of(double v) {
 }
 __device__ __forceinline__ double lane0_of(double v) { return lane_of<0>(v); }
 
+// The sum of x over the threads of a row held by WPR waves of a block (1, or
+// all of the block's), in every thread: lanes in lane order (wave_fold), then
+// the row's waves in wave order through sm (WPR doubles of LDS; every thread of
+// the block must call).  The rows kernels of bm_standardize.hip and bm_detrend.hip.
+template <int WPR> __device__ __forceinline__ double row_sum(double x, int lane, int wave, double *sm) {
+  x = wave_fold(x, lane, [](double a, double b) { return a + b; });
+  if constexpr (WPR == 1) {
+    return lane_of<kFoldLane>(x);
+  } else {
+    if (lane == kFoldLane) sm[wave] = x;
+    __syncthreads();
+    double t = sm[0];
+#pragma unroll
+    for (int w = 1; w < WPR; ++w) t += sm[w];
+    __syncthreads();  // sm is written again by the next sum
+    return t;
+  }
+}
+
 // ---- block order of the row kernels ----
 // Round-robin dispatch puts block b on XCD b % 8: give XCD x the x-th
 // contiguous eighth of the rows, so the 128-B lines two neighbouring rows

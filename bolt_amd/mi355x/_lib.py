@@ -20,6 +20,7 @@ COMOMENT_MAX_SIGNALS = 4   # BM_COMOMENT_MAX_SIGNALS
 COMOMENT_MAX_PARTS = 128   # BM_COMOMENT_MAX_PARTS
 QUANTILE_MAX_RANKS = 8     # BM_QUANTILE_MAX_RANKS
 NORM_MEAN, NORM_RANK = 0, 1  # BM_NORM_MEAN, BM_NORM_RANK
+DETREND_MAX_ORDER = 8      # BM_DETREND_MAX_ORDER
 
 LIB_PATH = os.environ.get("BOLT_AMD_LIB") or os.path.join(
     os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "libbolt_mi355x.so")  # env: A/B builds
@@ -73,6 +74,11 @@ SIGNATURES = {
                                        _c.c_int, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int), _c.c_void_p]),
     "bm_standardize_apply": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p]),
+    "bm_detrend_rows": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p,
+                                   _c.c_int, _c.c_int64, _c.POINTER(_c.c_int), _c.c_void_p]),
+    "bm_detrend_apply": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
+                                    _c.c_int64, _c.c_void_p]),
     "bm_reduce_state_bytes": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int64, _c.POINTER(_c.c_size_t)]),
     "bm_reduce_state": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64,
                                    _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),

@@ -423,6 +423,31 @@ class HipBackend(object):
         if rc:
             _lib.check(rc, "bm_standardize_apply")
 
+    def detrend_rows(self, src, code, O, R, src_pitch, order, dst, out_code, dst_pitch):
+        """dst rows = src rows minus their least-squares polynomial of degree
+        ``order`` (1.._lib.DETREND_MAX_ORDER, < R; the mean goes too), O rows
+        of R elements, pitches in elements: one read and one write
+        (bm_detrend_rows) -> True if the rows were taken, False (nothing
+        launched) when they do not fit the kernels."""
+        taken = ctypes.c_int(0)
+        rc = self.lib.bm_detrend_rows(src.data_ptr(), code, O, R, src_pitch, order, dst.data_ptr(), out_code,
+                                      dst_pitch, ctypes.byref(taken), raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_detrend_rows")
+        return bool(taken.value)
+
+    def detrend_apply(self, src, code, O, R, I, src_pitch, mean, coef, basis, order, dst, out_code, dst_pitch):
+        """dst[o,r,i] = (src[o,r,i] - mean[o*I+i]) - sum_k coef[k][o*I+i] basis[k][r]
+        with float64 device planes ``mean`` (O*I values) and ``coef``
+        (``order`` such planes) and the float64 device table ``basis``
+        (order x R, signal-major); rows ``src_pitch`` / ``dst_pitch`` elements
+        apart when I == 1 (bm_detrend_apply)."""
+        rc = self.lib.bm_detrend_apply(src.data_ptr(), code, O, R, I, src_pitch, mean.data_ptr(), coef.data_ptr(),
+                                       basis.data_ptr(), order, dst.data_ptr(), out_code, dst_pitch,
+                                       raw_stream(src.device))
+        if rc:
+            _lib.check(rc, "bm_detrend_apply")
+
     def comoment_state(self, src, code, O, R, I, pitch, y, ymean, yresid, state, workspace=None):
         """The co-moment state of one read of ``src`` ([O][R][I]; rows ``pitch``
         elements apart when I == 1) against the K signals ``y`` (device float64,

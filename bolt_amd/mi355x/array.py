@@ -1454,6 +1454,198 @@ class BoltArrayMI355X(BoltArray):
         throughout.  An addition to the reference's API."""
         return self._standardized(axis, True)
 
+    def _detrended(self, axis, order):
+        """detrend(): every record over ``axis`` minus its least-squares
+        polynomial of degree ``order``, as a new device array of this array's
+        shape and split in the dtype of ``record - 0.0``.  The fit is a
+        projection onto the discrete orthonormal polynomials p_1..p_order over
+        the record's positions (reduction.detrend_basis), of d = x - mean:
+        y = d - sum_k C_k p_k with C_k = sum d p_k, all float64.
+
+        Planned with reduction.plan_for like _standardized, and what it costs:
+          * the last axis (rows dense or row-padded, read in place), every
+            record on this rank: one bm_detrend_rows launch, one read and one
+            write; a padded input whose item size is kept gives a result
+            padded alike;
+          * rows that launch does not take, and reduced axes that form one
+            block: the float64 mean and C_k planes from bm_comoment_state with
+            the basis rows as the signals -- one read per batch of
+            _lib.COMOMENT_MAX_SIGNALS, so one for order <= 4 and two for 5..8
+            -- then bm_detrend_apply: one more read and one write;
+          * reduced axes that are not one block: permuted to the front first
+            and the result permuted back -- two more reads and writes;
+          * a row-padded input over other axes than the last: copied to a dense
+            temporary first (the array itself stays padded) -- one more read
+            and write;
+          * the sharded axis reduced: every rank's state over its slice of the
+            basis, gathered; the co-moments merged in rank order
+            (bm_comoment_combine as covariances, then one float64 multiply of
+            the planes by n) and the mean from the same states' (mean, M2)
+            planes (combine_moments), no second read; then applied to this
+            rank's slab with its slice of the basis.  A rank with an empty slab
+            launches nothing but takes part in every collective.
+        Moment states (KEEP_MOMENTS, swap states) are neither used nor left."""
+        ax = tupleize(list(range(len(self.shape))) if axis is None else axis)
+        inshape(self.shape, ax)
+        if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)):
+            raise ValueError("detrend: order must be an integer, got %r" % (order,))
+        order = int(order)
+        if not 0 <= order <= _lib.DETREND_MAX_ORDER:
+            raise ValueError("detrend: order must be in 0..%d, got %d" % (_lib.DETREND_MAX_ORDER, order))
+        n = self._nrecords(ax)
+        if self.size and order >= n:
+            raise ValueError("detrend: order %d needs records of more than %d values over axis %s (order < n)"
+                             % (order, n, tuple(ax)))
+        if order == 0:
+            return self.center(axis)
+        plan, out_dtype, ocode = reduction.plan_for(self, ax, reduction.STANDARDIZE)
+        code = plan.code
+        dev = self._device
+        if self.size == 0:
+            return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+        be = backend_for(dev)
+        perm, O, R, I, nloc = plan.perm, plan.O, plan.R, plan.I, plan.nloc
+        es, oes = self._dtype.itemsize, out_dtype.itemsize
+        d = self.__dict__
+        pbuf, P = d.get("_pbuf"), d.get("_pitch")
+        # every reduced record lies whole on this rank
+        local = plan.world == 1 or 0 not in plan.axes
+        # the reduced axis is the last one: rows, a pitch apart
+        rows_last = perm is None and I == 1 and local and (pbuf is None or R == plan.lshape[-1])
+
+        if rows_last and nloc and hasattr(be, "detrend_rows"):
+            keep_pad = pbuf is not None and oes == es
+            dp = P if keep_pad else R
+            dst = _empty(O * dp * oes, dev)
+            src, sp = (pbuf, P) if pbuf is not None else (self._data, R)
+            if be.detrend_rows(src, code, O, R, sp, order, dst, ocode, dp):
+                if not keep_pad:
+                    return self._like(dst, self._shape, self._split, dtype=out_dtype)
+                new = self._derive_padded(dst, P, self._shape, self._split)
+                new.__dict__["_dtype"] = out_dtype
+                return new
+
+        from bolt_amd.mi355x import functional as F
+        f64 = np.dtype(np.float64)
+        batch = _lib.COMOMENT_MAX_SIGNALS
+        basis = reduction.detrend_basis(n, order)
+        # a rank with an empty slab launches nothing, so it needs no source
+        src = reduction.source(self, plan, compact=True) if nloc else None
+        means, coefs = [], []   # per batch: the float64 mean plane, its C_k planes (uint8 tensors)
+        if local:
+            if not nloc:
+                return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+            nplane = O * I
+            mine = basis
+            for k0 in range(0, order, batch):
+                ys = basis[k0:k0 + batch]
+                ymean, yresid, _ = reduction.signal_centre(ys)
+                state = _empty((2 + len(ys)) * nplane * 8, dev)
+                reduction.comoment_state(be, src, self._dtype, code, ys, ymean, yresid, state)
+                means.append(state[:nplane * 8])
+                coefs.append(state[2 * nplane * 8:])
+        else:
+            # the sharded axis is reduced: one state per rank and batch over its
+            # slice of the basis (zeroes where its slab is empty), gathered;
+            # every rank takes part, its launches only where its slab has elements
+            ctx = self._ctx
+            if plan.world > min(_lib.COMOMENT_MAX_PARTS, _lib.MAX_COMBINE_PARTS):
+                raise NotImplementedError("detrend over the sharded axis merges at most %d ranks (got %d)"
+                                          % (min(_lib.COMOMENT_MAX_PARTS, _lib.MAX_COMBINE_PARTS), plan.world))
+            nplane = plan.nout
+            fcode = dtype_code(f64)
+            bounds = ctx.bounds(plan.shape[0])
+            per = n // plan.shape[0]
+            counts = [(hi - lo) * per for lo, hi in bounds]
+            # the record's positions run over the reduced axes in C order, the sharded axis first
+            table = basis.reshape(order, plan.shape[0], per)
+            lo, hi = bounds[ctx.rank]
+            mine = np.ascontiguousarray(table[:, lo:hi].reshape(order, -1))
+            for k0 in range(0, order, batch):
+                Kb = min(batch, order - k0)
+                parts = [reduction.signal_centre(table[k0:k0 + Kb, a:b].reshape(Kb, -1)) for a, b in bounds]
+                sbytes = (2 + Kb) * nplane * 8
+                state = _empty(sbytes, dev)
+                if nloc:
+                    reduction.comoment_state(be, src, self._dtype, code, mine[k0:k0 + Kb], parts[ctx.rank][0],
+                                             parts[ctx.rank][1], state)
+                else:
+                    state.zero_()
+                states = all_gather_bytes(ctx, state, [sbytes] * plan.world)
+                cov = _empty(Kb * nplane * 8, dev)
+                reduction.comoment_combine(be, _lib.CO_COV, states, counts, [p[0] for p in parts],
+                                           [reduction.signal_m2(p[2], p[1]) for p in parts], nplane, Kb, cov, f64,
+                                           fcode)
+                coefs.append(F.as_bytes(F.view(cov, (Kb, nplane), f64) * float(n)))
+                if not means:
+                    # the same states' (mean, M2) planes, part-major: a STAT_VAR state per rank
+                    mm = states.view(plan.world, 2 + Kb, nplane * 8)[:, :2, :].contiguous().view(-1)
+                    mean = _empty(nplane * 8, dev)
+                    reduction.combine_moments(be, code, fcode, ('mean',), mm, counts, nplane, [mean])
+                    means.append(mean)
+            if not nloc:
+                return self._like(_empty(0, dev), self._shape, self._split, dtype=out_dtype)
+
+        import torch
+        mean = means[0]
+        coef = coefs[0] if len(coefs) == 1 else torch.cat(coefs)
+        dst = _empty(nloc * oes, dev)
+        buf, pitch = src.buf, src.pitch
+        if hasattr(be, "detrend_apply"):
+            tab = torch.from_numpy(np.ascontiguousarray(mine).reshape(-1))
+            if dev.type == "cuda":
+                # page-locked + non-blocking, as comoment_state uploads its signals
+                tab = tab.pin_memory().to(dev, non_blocking=True)
+            be.detrend_apply(buf, code, O, R, I, pitch, mean, coef, F.as_bytes(tab), order, dst, ocode, R)
+        else:
+            # an executor without the entry points (the CPU test executor):
+            # torch float64 arithmetic on views of the bytes, padded rows
+            # through a strided view
+            if pitch != R:
+                x = F.view(buf[:O * pitch * es], (O, pitch), self._dtype)[:, :R].unsqueeze(2)
+            else:
+                x = F.view(buf, (O, R, I), self._dtype)
+            y = x.to(torch.float64) - F.view(mean, (O, 1, I), f64)
+            tab = torch.from_numpy(np.ascontiguousarray(mine)).to(dev)
+            c = F.view(coef, (order, O, 1, I), f64)
+            fit = c[0] * tab[0].reshape(1, R, 1)
+            for k in range(1, order):
+                fit = fit + c[k] * tab[k].reshape(1, R, 1)
+            dst = F.as_bytes((y - fit).to(F.torch_dtype(out_dtype)).contiguous())
+        if perm is not None:
+            back = _empty(nloc * oes, dev)
+            be.permute(dst, [plan.lshape[p] for p in perm], [int(i) for i in np.argsort(perm)], oes, back)
+            dst = back
+        return self._like(dst, self._shape, self._split, dtype=out_dtype)
+
+    def detrend(self, axis=None, order=1):
+        """Every record over ``axis`` (None: every axis, the whole array as one
+        record; taken as mean() takes it) minus its least-squares polynomial of
+        degree ``order``: the removal of slow drift that comes before dF/F,
+        z-scores or correlations (thunder's Series.detrend), as a new array of
+        the same shape, split and sharding, resident on the device; its dtype
+        is that of ``record - 0.0`` (float16 / float32 keep theirs, every other
+        dtype gives float64), as zscore() returns its result.  The fit is over
+        the record's positions 0..n-1; several reduced axes are flattened in C
+        order of the ascending axes, as cov() takes its signal.  The convention
+        is scipy.signal.detrend's: the mean goes too.  thunder instead zeroes
+        the fit's constant coefficient and so keeps the fitted value at
+        position 0; that variant is not offered.  ``order`` 0 returns
+        center(axis).  All arithmetic is float64 and the result is rounded
+        once; no Vandermonde matrix is formed: the record's deviations from its
+        mean (formed as center() forms it) are projected onto the discrete
+        orthonormal polynomials on its n positions, built by their three-term
+        recurrence.  A constant record gives exact zeros; for ``order`` >= 1 a
+        record holding a NaN or an infinity is NaN throughout, other records
+        are untouched; ``order`` = n - 1 interpolates, leaving rounding noise;
+        int64 / uint64 values beyond 2^53 round when converted to float64; bool
+        runs as uint8.  ``order`` that is not an integer (a bool is refused),
+        outside 0.._lib.DETREND_MAX_ORDER (8) or, for a non-empty array, not
+        below n raises ValueError before any device work.  Over the last axis
+        the array is read once and written once; what other layouts cost:
+        _detrended.  An addition to the reference's API."""
+        return self._detrended(axis, order)
+
     def _normalized(self, axis, method, perc, offset):
         """normalize(): every record over ``axis`` against its own baseline b,
         (x - b) / (b + offset), as a new device array of this array's shape and

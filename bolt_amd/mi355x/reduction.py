@@ -1,8 +1,8 @@
 """Mechanics of the statistics: how the reduced axes of an array lie in HBM and
 what is launched to reduce over them.  One plan, one source, one finish, for
 array.py's _reduced (one statistic), _reduced_moments (stats()),
-_standardized (center / zscore), _normalized (normalize), _comoment (cov / corr)
-and _quantile (quantile / percentile / median).  The rules -- what is kept, padded or fused,
+_standardized (center / zscore), _detrended (detrend), _normalized (normalize),
+_comoment (cov / corr) and _quantile (quantile / percentile / median).  The rules -- what is kept, padded or fused,
 and their switches -- stay in array.py; this module never imports it and is
 handed the array.
 """
@@ -378,6 +378,38 @@ def comoment_combine(be, what, states, counts, ymean, ym2, nout, K, out, out_dty
         r = torch.where(den > 0, torch.clamp(C / torch.sqrt(den), -1.0, 1.0),
                         torch.full_like(den, float("nan")))   # no variance, no correlation
     F.view(out, (K, nout), out_dtype).copy_(r.to(F.torch_dtype(out_dtype)))
+
+
+_BASES = {}  # (n, order) -> detrend_basis' table
+
+
+def detrend_basis(n, order):
+    """p_1..p_order, the discrete orthonormal (Gram) polynomials on the n
+    positions t_r = r - (n-1)/2, as an (order, n) float64 table (cached per
+    (n, order), shared by its callers: not to be written): bm_detrend_rows' recurrence in numpy float64,
+    b_k = (k/2) sqrt((n-k)(n+k) / (4k^2-1)), p_0 = 1/sqrt(n),
+    p_1 = t p_0 / b_1, p_{k+1} = (t p_k - b_k p_{k-1}) / b_{k+1}, multiplying
+    by 1/b_k as the kernel does.  No Vandermonde matrix is formed.  order < n."""
+    key = (int(n), int(order))
+    tab = _BASES.get(key)
+    if tab is None:
+        nf = np.float64(n)
+        t = np.arange(n, dtype=np.float64) - (nf - 1.0) / 2.0
+        k = np.arange(1, order + 1, dtype=np.float64)
+        b = k / 2.0 * np.sqrt((nf - k) * (nf + k) / (4.0 * k * k - 1.0))
+        rb = 1.0 / b
+        tab = np.empty((order, n), dtype=np.float64)
+        pm = np.full(n, 1.0 / np.sqrt(nf))
+        pk = t * pm * rb[0]
+        tab[0] = pk
+        for q in range(1, order):
+            pn = (t * pk - b[q - 1] * pm) * rb[q]
+            pm, pk = pk, pn
+            tab[q] = pk
+        if len(_BASES) >= 8:   # (tables of long records are megabytes)
+            _BASES.clear()
+        _BASES[key] = tab
+    return tab
 
 
 def quantile_rows(be, buf, dtype, code, O, R, pitch, ranks, frac, out, out_dtype, ocode):

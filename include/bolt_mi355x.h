@@ -390,6 +390,64 @@ int bm_standardize_apply(const void *src, int in_dtype, int64_t O, int64_t R,
                          int64_t dst_pitch, void *stream);
 
 /*
+ * bm_detrend_rows -- every row minus its least-squares polynomial of degree
+ * `order` (1..BM_DETREND_MAX_ORDER, and < R) in one read and one write:
+ *   dst[o*dst_pitch + r] = d_r - sum_{k=1..order} C_k p_k(t_r),  r < R,
+ * d_r = src[o*src_pitch + r] - mean_o.  No reference call site: the reference
+ * has no detrend (an API addition, like bm_standardize_rows' center / zscore);
+ * thunder's Series.detrend fits every record on the host.  The convention is
+ * scipy.signal.detrend's: the mean goes with the trend.  Pitches are in
+ * elements, >= R; the pad is neither read nor written.  out_dtype must be the
+ * statistics dtype of in_dtype (float16 / float32 keep theirs, every other
+ * dtype gives float64).  Numerics, all float64: no Vandermonde matrix is
+ * formed; p_k are the discrete orthonormal (Gram) polynomials on the row's R
+ * positions, t_r = r - (R-1)/2, b_k = (k/2) sqrt((R-k)(R+k) / (4k^2-1)),
+ *   p_0 = 1/sqrt(R), p_1 = t p_0 / b_1, p_{k+1} = (t p_k - b_k p_{k-1}) / b_{k+1}
+ * (b_k and 1/b_k formed on the host, the kernel multiplies by the reciprocal;
+ * no table is read: every lane walks the recurrence over the positions it
+ * holds); mean_o is bm_standardize_rows' two-pass mean about the row's first
+ * element, C_k = sum_r d_r p_k(t_r) summed in a fixed order (the same input
+ * gives the same bytes), the fit is summed k ascending and the result rounded
+ * once to out_dtype.  Each row is held in registers between its read and its
+ * write, as bm_standardize_rows holds it, and *taken follows the same plan:
+ * 1 when the rows were written; 0 and nothing launched when a row is longer
+ * than the kernels hold on chip, or when longer rows are too few to give each
+ * a block (bm_comoment_state with the basis as the signals, then
+ * bm_detrend_apply, serve those).  A constant row gives exact zeros; a nan or
+ * an infinity makes its whole row nan.  O == 0 or R == 0 writes nothing
+ * (*taken = 1).  Arguments are checked before any launch; a refused call
+ * leaves *taken alone.
+ */
+#define BM_DETREND_MAX_ORDER 8   /* two batches of BM_COMOMENT_MAX_SIGNALS */
+int bm_detrend_rows(const void *src, int in_dtype, int64_t O, int64_t R,
+                    int64_t src_pitch, int order, void *dst, int out_dtype,
+                    int64_t dst_pitch, int *taken, void *stream);
+
+/*
+ * bm_detrend_apply -- the elementwise half of detrend for every layout
+ * bm_detrend_rows does not take: over bm_reduce's [O][R][I],
+ *   dst[o,r,i] = (src[o,r,i] - mean[o*I+i]) - sum_{k<order} coef[k*O*I + o*I+i] * basis[k*R + r],
+ * mean being a float64 device plane of O*I values, coef `order` such planes
+ * (bm_comoment_state's mean and C planes against the basis) and basis
+ * order x R float64 values in device memory, signal-major: p_1..p_order of
+ * bm_detrend_rows at the R positions.  No reference call site (an API
+ * addition, see bm_detrend_rows).  With I == 1 the rows of src / dst are
+ * src_pitch / dst_pitch elements apart (>= R); with I > 1 both pitches must be
+ * R.  out_dtype is bm_detrend_rows'; the subtraction of the mean, the fit
+ * (summed k ascending) and its subtraction are float64, rounded once.  Planes
+ * and basis are read through the cache, the array with streaming loads and
+ * stores: one read and one write of the array.  order outside
+ * 1..BM_DETREND_MAX_ORDER gives BM_E_ARG; order >= R is taken, unlike
+ * bm_detrend_rows: the table is the caller's, and R may be one rank's slab of
+ * a record that is spread over ranks, shorter than the fit has terms.  Any of
+ * O, R, I == 0 writes nothing.  Arguments are checked before any launch.
+ */
+int bm_detrend_apply(const void *src, int in_dtype, int64_t O, int64_t R,
+                     int64_t I, int64_t src_pitch, const double *mean,
+                     const double *coef, const double *basis, int order,
+                     void *dst, int out_dtype, int64_t dst_pitch, void *stream);
+
+/*
  * Partial reduction state for the multi-GPU merge (the per-partition
  * StatCounter of array.py:321-322).  `state` receives, for O*I outputs:
  *   MEAN/VAR/STD: two float64 planes, mean[O*I] then M2[O*I] (count = R);
