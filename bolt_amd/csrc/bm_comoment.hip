@@ -46,6 +46,15 @@
 //   for n up to 1e7.  Every signal's sums are its own and take the same order
 //   whatever K is (explicit fma, no contraction across signals): plane k of a
 //   K-signal call has the bits of the one-signal call.  No float atomics.
+//   Non-finite records are numpy's: the pivot is finite -- a first element that
+//   is an infinity or a NaN takes 0 (finite_or_zero, as in bm_reduce.hip) -- so
+//   the mean plane is what a sum over the record gives (+inf, -inf, or NaN for
+//   inf - inf or a NaN) wherever the value sits, and M2 = inf - inf = NaN
+//   exactly when the record holds such a value.  Sxy - (S1 / n) * yresid is
+//   then +-inf or NaN by the sign of a rounding residue, so store_sums makes
+//   every co-moment NaN where M2 came out NaN: one compare and select per
+//   output; finite records keep their bits.  k_co_combine needs no more: a NaN
+//   M2 or C of any part reaches the merged values through its fmas.
 #include "bm_common.h"
 #include "bm_host.h"
 #include "bm_wave.h"
@@ -98,11 +107,14 @@ __device__ __forceinline__ void store_sums(double *__restrict__ state, double *_
   }
   const double dm = s1 / n;
   const double m2 = fma(-s1, dm, s2);
-  state[e] = P + dm;
+  state[e] = P + dm;  // (P is finite: an infinite S1 gives the sum's mean)
   state[nout + e] = m2 < 0.0 ? 0.0 : m2;  // (a nan stays a nan)
+  // a record holding a nan or an infinity: M2 is nan (inf - inf), and so is every
+  // co-moment, whatever Sxy - inf * resid came to; finite records keep their bits
+  const bool spoilt = m2 != m2;
 #pragma unroll
   for (int k = 0; k < KT; ++k)
-    if (k < K) state[(2 + k) * nout + e] = fma(-dm, ys.resid[k], sxy[k]);
+    if (k < K) state[(2 + k) * nout + e] = spoilt ? m2 : fma(-dm, ys.resid[k], sxy[k]);
 }
 
 // VEC float64 values from LDS, 16 B at a time where the vector allows
@@ -165,7 +177,7 @@ __global__ void __launch_bounds__(64 * rows_waves(KT))
     if (row >= d.O) return;
     const T *base = src + row * d.P;
     const T *s = base + r_lo;
-    const double P = to_f64(base[0]);
+    const double P = finite_or_zero(to_f64(base[0]));
     double s1 = 0.0, s2 = 0.0, sxy[KT];
 #pragma unroll
     for (int k = 0; k < KT; ++k) sxy[k] = 0.0;
@@ -330,7 +342,7 @@ __global__ void __launch_bounds__(kThreads)
     T p0[VEC];
     vload<T, VEC>(base, p0);  // the pivot: the column's element in row 0, shared by chunks and phases
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) P[i] = to_f64(p0[i]);
+    for (int i = 0; i < VEC; ++i) P[i] = finite_or_zero(to_f64(p0[i]));
     if (d.tcv == 64)
       cols_sums<T, VEC, KT, true>(base, y, d, ys, r_lo + ph, r_hi, P, s1, s2, sxy);
     else

@@ -1920,8 +1920,11 @@ class BoltArrayMI355X(BoltArray):
         ``keepdims`` re-inserts the reduced axes after the K axis) and the
         statistics dtype (float16 / float32 keep theirs, every other dtype
         gives float64).  The arithmetic is float64, rounded once; a constant
-        record or signal gives 0; a nan in a record reaches its outputs only;
-        no records give nan.  Plane k of a K-signal call has the bytes of the
+        record or signal gives 0; a record holding a NaN or an infinity gives
+        NaN, as numpy's x - mean(x) makes it (inf - inf), wherever in the
+        record the value sits, and other records are untouched (the co-moment
+        state's mean plane of such a record is what a sum over it gives: +inf,
+        -inf, or NaN for inf - inf or a NaN); no records give nan.  Plane k of a K-signal call has the bytes of the
         one-signal call with y[k].  An addition to the reference's API."""
         return self._comoment(y, axis, keepdims, _lib.CO_COV)
 
@@ -1929,7 +1932,8 @@ class BoltArrayMI355X(BoltArray):
         """Pearson correlation cov(y) / (std_x std_y) of every record over
         ``axis`` with the signal(s) ``y``, taken and returned as cov() takes and
         returns them; clamped to [-1, 1] before the one rounding, as
-        numpy.corrcoef does.  A record or a signal of zero variance gives nan.
+        numpy.corrcoef does.  A record or a signal of zero variance gives nan,
+        and so does a record holding a NaN or an infinity, as for cov().
         An addition to the reference's API."""
         return self._comoment(y, axis, keepdims, _lib.CO_CORR)
 

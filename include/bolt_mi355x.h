@@ -525,8 +525,11 @@ int bm_comoment_workspace_bytes(int in_dtype, int64_t O, int64_t R, int64_t I,
  * accumulation is float64 about the record's first element, summed in a fixed
  * order (lanes, row phases, chunks: see bm_comoment.hip): the same input gives
  * the same bytes, and plane k has the bytes of the one-signal call with y_k.
- * workspace: bm_comoment_workspace_bytes (BM_E_WS if smaller).  A nan in a
- * record reaches that record's values only.  Any of O, R, I == 0 stores
+ * workspace: bm_comoment_workspace_bytes (BM_E_WS if smaller).  A record
+ * holding a nan or an infinity has a nan M2 and nan C_k, and the mean a sum
+ * over it gives (+inf, -inf, or nan for inf - inf or a nan), wherever in the
+ * record the value sits (the pivot is finite: such a first element takes 0);
+ * other records are untouched.  Any of O, R, I == 0 stores
  * nothing.  Arguments are checked before any launch: null pointers, a bad
  * dtype, negative extents, a pitch below R or a pitch with I > 1, K outside
  * 1..BM_COMOMENT_MAX_SIGNALS give BM_E_ARG.
@@ -547,6 +550,9 @@ int bm_comoment_state(const void *src, int in_dtype, int64_t O, int64_t R,
  *   what = BM_CO_CORR: C / sqrt(M2_x M2_y), clamped to [-1, 1] before the one
  *                      rounding; nan unless M2_x M2_y > 0 (a record or a
  *                      signal of zero variance, whatever rounding left in C).
+ * A record that holds a nan or an infinity in any part (a nan M2 and C_k in
+ * that part's state) gives nan, cov and corr alike; the merged mean is not
+ * an output.
  * No reference call site: an API addition.  counts[nparts] (parts of count 0
  * are skipped; all 0: nan), ymean[nparts*K] and ym2[nparts*K] (each part's
  * own mean and sum of squared deviations of its slice of signal k, part-major)

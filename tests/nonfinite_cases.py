@@ -1,5 +1,6 @@
-"""Rows that hold a NaN or an infinity, for test_zzzz_nonfinite_moments.py: the
-arrays, and the truth of their mean / var / std.
+"""Rows that hold a NaN or an infinity, for test_zzzz_nonfinite_moments.py and
+test_zzzzzz_nonfinite_comoment.py: the arrays, and the truth of their mean /
+var / std, cov / corr and detrend.
 
 The contract is numpy's: the mean of such a row is what a sum over it gives
 (+inf, -inf, or NaN for inf - inf or a NaN), its var and std are NaN.  The
@@ -11,7 +12,16 @@ var / std on every array of this module, which makes numpy the reference.
 "Diagonal" arrays mark row i of a finite base at column i, so one launch tries
 every position of the reduced axis -- pivot, main loop, tail, chunk starts,
 last element -- without the test knowing the kernel's plan.  Where one long
-row is reduced a diagonal is impossible; the dense patterns stand in.
+row is reduced a diagonal is impossible; the dense patterns stand in.  Where
+an array has fewer rows than positions, marked_columns lists the positions
+that matter: both ends, the middle, and both sides of every chunk boundary.
+
+cov(), corr() and detrend() of such a record are NaN -- detrend() on every
+element of it -- as numpy's own float64 formulas give (x - mean(x) holds
+inf - inf, or the NaN); Truth.bad is that classification, and
+test_zzzzzz_nonfinite_comoment.py's test_truth_is_numpys holds it to numpy.
+The records beside them are held to the methods' own truths and bounds
+(comoment_cases, detrend_cases), computed on Truth.xfine.
 """
 import functools
 
@@ -46,15 +56,48 @@ def base(nrows, n, dtype, seed=0):
     return _base(int(nrows), int(n), np.dtype(dtype).name, int(seed))
 
 
-def diagonal(n, dtype, variant, nrows=None, seed=0):
+CHUNK = 2048  # bm_comoment.hip's kRowsChunk: the elements of a row one wave sums
+
+
+def marked_columns(n, chunk=CHUNK):
+    """The positions of a record of ``n`` values a shape with few rows marks:
+    0, 1, the last, the middle, and both sides of every multiple of ``chunk``
+    below n."""
+    cols = {0, 1, n - 1, n // 2}
+    for m in range(chunk, n, chunk):
+        cols |= {m - 1, m}
+    return sorted(c for c in cols if 0 <= c < n)
+
+
+def diagonal(n, dtype, variant, nrows=None, seed=0, cols=None):
     """(nrows, n): row i < n marked at column i by ``variant``, the rows from
-    n on (nrows defaults to n + 2) left finite."""
+    n on (nrows defaults to n + 2) left finite.  ``cols``: row i marked at
+    column cols[i] instead, the rows from len(cols) on left finite."""
     nrows = n + 2 if nrows is None else nrows
     x = base(nrows, n, dtype, seed).copy()
-    i = np.arange(min(n, nrows))
+    if cols is None:
+        c = np.arange(min(n, nrows))
+    else:
+        c = np.asarray(cols, dtype=np.int64)
+        assert len(c) <= nrows and c.min() >= 0 and c.max() < n
+    i = np.arange(len(c))
     for value, col in VARIANTS[variant]:
-        x[i, col(i, n)] = value
+        x[i, col(c, n)] = value
     return x
+
+
+def finite_twin(x):
+    """``x`` with its non-finite values replaced by 10 (the base's centre): what the signals are drawn from."""
+    return np.where(np.isfinite(x), x, 10).astype(x.dtype)
+
+
+def records(x, axis):
+    """``x`` as (outputs, n): the kept axes flattened in their order, the
+    reduced ones (``axis``: an int, a tuple or None) in ascending order."""
+    x = np.asarray(x)
+    ax = tuple(range(x.ndim)) if axis is None else tuple(sorted(a % x.ndim for a in np.atleast_1d(axis).tolist()))
+    kept = [i for i in range(x.ndim) if i not in ax]
+    return x.transpose(kept + list(ax)).reshape(int(np.prod([x.shape[i] for i in kept], dtype=np.int64)), -1)
 
 
 # one long row: (name, sign-free description); every chunk's first element is
@@ -101,8 +144,8 @@ class Truth(object):
         x = np.asarray(x)
         ax = tuple(range(x.ndim)) if axis is None else tuple(sorted(np.atleast_1d(axis).tolist()))
         kept = [i for i in range(x.ndim) if i not in ax]
-        rows = x.transpose(kept + list(ax)).reshape(int(np.prod([x.shape[i] for i in kept], dtype=np.int64)), -1)
-        nan = np.isnan(rows).any(axis=1)
+        rows = records(x, ax)
+        nan =np.isnan(rows).any(axis=1)
         pinf = (rows == INF).any(axis=1)
         ninf = (rows == -INF).any(axis=1)
         self.bad = nan | pinf | ninf
@@ -172,6 +215,15 @@ def permuted(variant):
     return np.ascontiguousarray(rows.reshape(6, 10, 50).transpose(0, 2, 1)), 1
 
 
+MARKED_ROWS = (40, 2052)   # fewer rows than positions: marked_columns
+
+
+def marked(variant, dtype="float32"):
+    """MARKED_ROWS: row i marked at marked_columns(2052)[i], the other rows finite -> (array, axis)."""
+    nrows, n = MARKED_ROWS
+    return diagonal(n, dtype, variant, nrows=nrows, cols=marked_columns(n)), 1
+
+
 def swapped(n, a, b, dtype, variant):
     """(n, a, b) with a * b == n whose swap to (a, b, n) has the diagonal over
     n as its rows."""
@@ -200,6 +252,8 @@ def every_array():
         s = np.ascontiguousarray(swapped(500, 20, 25, "float32", variant).transpose(1, 2, 0))
         for axis in (2, 0, None):
             yield "padded-%s-%s" % (axis, variant), s, axis
+        x, axis = marked(variant)
+        yield "marked-%s" % variant, x, axis
     for dtype in ("float32", "float64"):
         for p in DENSE:
             yield "dense-%s-%s" % (dtype, p), dense(DENSE_N, dtype, p), None
